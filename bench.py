@@ -1,23 +1,27 @@
 #!/usr/bin/env python3
 """bench.py -- the headline benchmark of BASELINE.json on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size-gib G] [--block B] [--codec NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size-gib G] [--block B] [--codec NAME] [--dump-outputs DIR] [--full]
 
 Workload (N = 1): `rle8_packed_multi` -- 8 bit Packed, the north-star codec -- on an 8 GiB run-distributed(8) synthetic buffer
 (BASELINE.json: "8-bit Packed decode of an 8 GiB synthetic buffer at 1 GPU"), cut into 4 KiB blocks that are each a
 complete reference stream.  A STEP is one decode of the whole container, device resident (compressed container and output both in
-HBM).  `value` = uncompressed GiB decoded per second (the reference's own unit, src/main.c:875,:1014); the encode throughput of
-the same buffer is reported next to it ("encode").  For N > 1 every rank owns its own 8 GiB shard (weak scaling, block-sharded,
-no data-path collective: SURVEY.md §8e); the RCCL gather of the compressed segments into one stream is timed separately
+HBM).  `value` = uncompressed GiB decoded per second (the reference's own unit, src/main.c:875,:1014); with --full the encode throughput
+of the same buffer is reported next to it ("encode").  For N > 1 every rank owns its own 8 GiB shard (weak scaling, block-sharded,
+no data-path collective: SURVEY.md §8e); with --full the RCCL gather of the compressed segments into one stream is timed separately
 ("gather_ms") because it is not part of the decode path.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, the workload); with
+--dump-outputs DIR it then writes what the last timed step handed its caller (dump_outputs).  --full adds everything else, measured
+after the timed steps (--no-cpu, --no-extras and --no-config5 leave parts of it out):
   roofline      HBM roofline of the decode kernel: algorithmic bytes (compressed + uncompressed) / average kernel
                 duration measured with HIP events on the launch stream, against the 8 TB/s peak
   cpu_baseline  the same decode on the host CPU, one thread, on a bounded sample of the same workload: the compiled reference
                 (oracle/_ref, kind "reference") when it is present, else the oracle's restatement (kind "port"); encode.cpu_baseline is
                 the encode direction of the same sample (BASELINE metric: "decode + encode GiB/s ... vs CPU")
   bit_exact     block streams of a sample equal the CPU codec's streams and the full decode equals the input
+  encode        the encode throughput of the same buffer
+  extras        BASELINE configs 3 and 5, the monolithic 1 GiB stream, the host-pointer drop-in path, video-shaped and 64 KiB-block rows
 """
 import argparse
 import ctypes
@@ -440,6 +444,37 @@ def video_rows(hsrle, torch, dev, with_cpu, kind=None, block=4096, keys=("rle8_p
     return rows
 
 
+DUMP_SAMPLE = 1 << 22   # decoded bytes sampled by --dump-outputs
+DUMP_CHUNK = 1 << 20    # bytes per sum in decoded_mib_sums.npy
+
+
+def dump_outputs(dirname, out, status):
+    """--dump-outputs DIR: what the last timed decode handed its caller, for comparing two builds output for output (the inputs depend on
+    the arguments only).  Written as .npy, about 16 MiB for the 8 GiB workload:
+      decoded_sample.npy    float32, the decoded bytes at DUMP_SAMPLE positions drawn with numpy seed 0 (sorted; the same for every run
+                            with the same output size)
+      decoded_mib_sums.npy  float64, the sum of the decoded bytes of every DUMP_CHUNK bytes (the last sum over what is left): covers every byte
+      status.npy            float64, the status words of the decode (word 0 = 0: success)"""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    n = out.numel()
+    idx = np.sort(np.random.default_rng(0).integers(0, n, size=min(n, DUMP_SAMPLE), dtype=np.int64))
+    sample = out[torch.from_numpy(idx).to(out.device)].to(torch.float32).cpu().numpy()
+    full = n // DUMP_CHUNK
+    sums = []
+    for r in range(0, full, 256):   # 256 MiB at a time: the int32 copy stays at 1 GiB (a sum stays below 2**28: exact in int32)
+        rows = min(256, full - r)
+        sums.append(out[r * DUMP_CHUNK : (r + rows) * DUMP_CHUNK].view(rows, DUMP_CHUNK).to(torch.int32).sum(dim=1, dtype=torch.int32))
+    if n % DUMP_CHUNK:
+        sums.append(out[full * DUMP_CHUNK :].to(torch.int32).sum(dtype=torch.int32).reshape(1))
+    sums = torch.cat(sums).cpu().numpy().astype(np.float64)
+    np.save(os.path.join(dirname, "decoded_sample.npy"), sample)
+    np.save(os.path.join(dirname, "decoded_mib_sums.npy"), sums)
+    np.save(os.path.join(dirname, "status.npy"), status.cpu().numpy().astype(np.float64))
+
+
 def kernel_name(codec_key):
     """The decode kernel instantiation behind a codec id (hsrle_decode.hip.h: k_decode_blocks<FAM, S, AL, T, R, Q, SGL>)."""
     from hsrle_testlib import CODEC_BY_KEY, FAMILY_NAMES
@@ -500,10 +535,15 @@ def main():
     ap.add_argument("--block", type=int, default=4096)
     ap.add_argument("--codec", default="rle8_packed_multi")
     ap.add_argument("--synth", choices=["runs", "video"], default="runs", help="synthetic generator: run-distributed (headline) or video-shaped (BASELINE config 3)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extras", action="store_true", help="skip the side measurements (config 3 frame, monolithic 1 GiB stream, config 5 rows)")
-    ap.add_argument("--no-config5", action="store_true", help="skip the sixteen 8 GiB codec rows of BASELINE config 5 (extras.config5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed to DIR/*.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true", help="after the headline, measure and check everything else: bit_exact, encode, roofline, cpu_baseline, "
+                                                        "extras, the gather step of N > 1")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the side measurements (config 3 frame, monolithic 1 GiB stream, config 5 rows)")
+    ap.add_argument("--no-config5", action="store_true", help="with --full: skip the sixteen 8 GiB codec rows of BASELINE config 5 (extras.config5)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process becomes the launcher.  It has not touched the GPU (no torch import,
@@ -593,6 +633,34 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, status)
+
+    headline = {
+        "metric": "rle8_extreme Packed decode throughput, uncompressed bytes (device resident block container)",
+        "value": round(size * world / 2**30 / (wall / args.steps), 2),
+        "unit": "GiB/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(wall / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic",
+        "config": {"workload": f"{args.codec} decode, {size / 2**30:g} GiB {synth_name} synthetic per GPU (seed {seed}), {args.block} B blocks, "
+                               f"ratio {info.totalSize / size:.4f}", "codec": args.codec, "block_size": args.block, "blocks_per_gpu": info.blockCount, "sharding": f"blocks x{world}"},
+        "library_build_id": hsrle.build_id(),
+    }
+    if not args.full:
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(result_fd, (json.dumps(headline) + "\n").encode())
+        if distributed:
+            dist.destroy_process_group()
+        return
+
     # ---- correctness (untimed): the decode equals the input, and EVERY block stream is the reference encoder's -- through the device
     #      hash of every block and the per-256-block roll-ups minted from the compiled reference (tests/golden/big/); a workload that has
     #      no manifest (non-default --codec / --size-gib / --block) is checked on a 16 MiB sample against the oracle ----
@@ -681,21 +749,8 @@ def main():
         total_units = size * world
         alg_bytes = size + info.totalSize
         achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
-        line = {
-            "metric": "rle8_extreme Packed decode throughput, uncompressed bytes (device resident block container)",
-            "value": round(total_units / 2**30 / (wall / args.steps), 2),
-            "unit": "GiB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(wall / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic",
-            "config": {"workload": f"{args.codec} decode, {size / 2**30:g} GiB {synth_name} synthetic per GPU (seed {seed}), {args.block} B blocks, "
-                                   f"ratio {info.totalSize / size:.4f}", "codec": args.codec, "block_size": args.block, "blocks_per_gpu": info.blockCount, "sharding": f"blocks x{world}"},
+        line = dict(headline)
+        line.update({
             "bit_exact": bool(ok),
             "parity": parity,
             "encode": {"value": round(size / 2**30 / (enc_ms * 1e-3), 2), "unit": "GiB/s", "ms": round(enc_ms, 4), "note": "same buffer: position-parallel encoder = sizes + records launch, size scan, emission launch (no staging slots, no compaction)",
@@ -706,7 +761,7 @@ def main():
                          "traffic": traffic, "traffic_source": "committed PMC passes of this build and this workload (profiles/, tools/traffic.sh): not a measurement of this run", "traffic_detail": traffic_detail, "kernel": kernel_name(args.codec), "waves_per_cu": hsrle.kernel_waves_per_cu(args.codec, True), "kernel_ms": round(kernel_ms, 4),
                          "algorithmic_bytes": int(alg_bytes),
                          "note": "algorithmic bytes = container (compressed) + uncompressed output per launch; traffic = upper bound of the PMC passes in profiles/ (128 B per counted fabric read request + WRITE_SIZE), lower bound in traffic_detail"},
-        }
+        })
         if gather_ms is not None:
             # the one exchange step of the sharded path ("aggregate GiB/s with and without the gather"): what the root receives
             # over xGMI -- every other rank's compressed segment -- against the time from the common start to the slowest rank's completion;
@@ -721,7 +776,6 @@ def main():
             line["rccl_ranks_source"] = rccl_via
             line["per_rank_bit_exact"] = per_rank_exact
             line["per_rank_library_build_id"] = per_rank_build
-        line["library_build_id"] = hsrle.build_id()
         if extras:
             line["extras"] = extras
         run_config5 = extras is not None and not args.no_extras and not args.no_config5 and args.codec == "rle8_packed_multi" and args.synth == "runs" and world == 1

@@ -29,6 +29,16 @@ def test_gpus_must_match_world_size():
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr and r.stdout.strip() == ""
 
 
+def test_steps_must_be_positive():
+    r = _run(["--steps", "0"])
+    assert r.returncode == 2 and "--steps" in r.stderr and r.stdout.strip() == ""
+
+
+def test_full_and_dump_outputs_are_options():
+    r = _run(["--full", "--dump-outputs", "unused"])
+    assert r.returncode == 0 and json.loads(r.stdout)["dryrun"] is True
+
+
 def test_launcher_env_is_honoured():
     r = _run(["--gpus", "2"], WORLD_SIZE="2", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29512")
     assert r.returncode == 0 and json.loads(r.stdout)["n_gpus"] == 2

@@ -110,7 +110,7 @@ def test_bench_distributed_leg_runs_as_a_world_of_one(c_abi):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", HSRLE_FORCE_DIST="1", HSRLE_DIST_C="1" if c_abi else "0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--size-gib", "1", "--no-extras", "--steps", "5", "--warmup", "2"], env=env, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--size-gib", "1", "--no-extras", "--steps", "5", "--warmup", "2"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

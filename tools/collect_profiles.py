@@ -12,7 +12,7 @@ d = json.loads(line)
 rows = list(csv.DictReader(open(src + "/stats/k_kernel_stats.csv")))
 trace = list(csv.DictReader(open(src + "/stats/k_kernel_trace.csv")))
 with open(f"{P}/{tag}_rocprof_summary.txt", "w") as f:
-    f.write(f"rocprofv3 --kernel-trace --stats -- python3 bench.py --no-extras   (library build {d.get('library_build_id', '?')})\n")
+    f.write(f"rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-extras   (library build {d.get('library_build_id', '?')})\n")
     f.write("bench line of the default run (with extras): value %.1f GiB/s, ms_per_step %.4f, roofline.kernel_ms %.4f, frac %.4f; encode %.1f GiB/s (%.4f)\n\n"
             % (d["value"], d["ms_per_step"], d["roofline"]["kernel_ms"], d["roofline"]["frac"], d["encode"]["value"], d["encode"]["roofline"]["frac"]))
     f.write("%-90s %8s %12s %12s %12s %7s\n" % ("kernel", "calls", "avg us", "min us", "max us", "%"))

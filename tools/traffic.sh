@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage (GPU box, via gpurun): bash tools/traffic.sh [tag]  -> gpurun_out/traffic_<tag>/traffic.json (copy it to profiles/<round>_traffic.json)
-# HBM traffic of the headline kernels of THIS build: rocprofv3 PMC passes over `bench.py --steps 3 --warmup 1 --no-cpu --no-extras` (one
+# HBM traffic of the headline kernels of THIS build: rocprofv3 PMC passes over `bench.py --full --steps 3 --warmup 1 --no-cpu --no-extras` (one
 # counter group per pass; no side measurements, so every counted launch of a kernel name IS the headline launch), averaged per launch, with
 # the launch counts and the library's build id (bench.py refuses the file for any other build).
 tag=${1:-run}
@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/traffic_$tag; mkdir -p $O; cd $R
 for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum" "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum"; do
   n=$(echo $grp | tr ' ' '_' | cut -c1-30)
-  timeout -k 5 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $O/pmc_$n -o p -- python3 bench.py --steps 3 --warmup 1 --no-cpu --no-extras > $O/pmc_$n.log 2> $O/pmc_$n.err || echo "pass failed: $grp"
+  timeout -k 5 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $O/pmc_$n -o p -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu --no-extras > $O/pmc_$n.log 2> $O/pmc_$n.err || echo "pass failed: $grp"
 done
 python3 - "$O" <<'PY'
 import csv, glob, collections, json, os, sys
@@ -43,7 +43,7 @@ lo, hi = container, req * 128
 enc_lo = sum(int((e[k]["FETCH_SIZE"] + e[k]["WRITE_SIZE"]) * 1024) for k in e)
 enc_hi = sum(int(e[k]["TCC_EA0_RDREQ_sum"] * 128 + e[k]["WRITE_SIZE"] * 1024) for k in e)
 out = {"codec": line["config"]["codec"], "size": size, "block": int(line["config"]["block_size"]), "library_build_id": hsrle.build_id(),
-       "source": "tools/traffic.sh: rocprofv3 --pmc, one counter group per pass, bench.py --steps 3 --warmup 1 --no-cpu --no-extras; averages per launch",
+       "source": "tools/traffic.sh: rocprofv3 --pmc, one counter group per pass, bench.py --full --steps 3 --warmup 1 --no-cpu --no-extras; averages per launch",
        "launches": {"decode": n_dec, "compress_calls": n_enc}, "raw_counters_per_launch": d, "container_bytes": container,
        "fetch_size_raw_bytes": fetch_raw, "write_bytes": write, "fabric_read_requests": req,
        "fetch_lower_bound_bytes": lo, "fetch_upper_bound_bytes": hi, "traffic_lower_bound_bytes": lo + write, "traffic_upper_bound_bytes": hi + write,
