@@ -18,7 +18,8 @@ namespace hsrle {
 template <int FAM>
 __global__ __launch_bounds__(64) void k_decode8_pe(const uint8_t *__restrict__ payload, const uint64_t *__restrict__ offsets, const uint8_t *__restrict__ payloadEnd,
                                                    uint8_t *__restrict__ out, uint64_t U, uint32_t B, uint32_t firstBlock, uint32_t blockCount, uint32_t *__restrict__ status,
-                                                   const uint32_t *__restrict__ entries, uint32_t entryBase, const uint32_t *__restrict__ gate)
+                                                   const uint32_t *__restrict__ entries, uint32_t entryBase, const uint32_t *__restrict__ gate,
+                                                   uint32_t, uint64_t, uint64_t)   // (gateWords, output window: not supported here -- the range decode does not launch this kernel)
 {
   static_assert(FAM == PLAIN || FAM == PACKED, "rle8_multi / rle8_packed_multi");
   using TR = Traits<FAM, 1, 0>;

@@ -1037,7 +1037,7 @@ struct MonoPlan
 //  *_mono_dev() can make that workspace too small, which that call reports as HSRLE_ERR_CAPACITY; include/hsrle.h says so)
 static std::atomic<uint32_t> g_monoTune[3] = { { env_u32("HSRLE_MONO_BLOCK", 0) }, { env_u32("HSRLE_MONO_REGION", 0) }, { env_u32("HSRLE_MONO_LOOKBACK", 0) } };
 
-static MonoPlan plan_mono(int codec, uint32_t U, uint32_t C, uint32_t p0)
+static MonoPlan plan_mono(int codec, uint32_t U, uint32_t C, uint32_t p0, uint32_t spacing = 0u)
 {
   MonoPlan m;
   // output bytes per decode lane: enough lanes to fill the GPU (>= 2^18 where the stream allows it), at most the container's 4 KiB
@@ -1048,6 +1048,7 @@ static MonoPlan plan_mono(int codec, uint32_t U, uint32_t C, uint32_t p0)
   G = G < 2048u ? 2048u : (G > 8192u ? 8192u : G);
   const uint32_t tB = g_monoTune[0], tG = g_monoTune[1], tM = g_monoTune[2];   // tuning / test knobs (hsrle_mono_tuning, HSRLE_MONO_* in the environment)
   if (tB >= 128u && tB <= (1u << 20) && (tB % 128u) == 0u) B = tB;
+  if (spacing != 0u) B = spacing;                                            // (a persistent index: the caller's record spacing, validated by the caller)
   if (tG >= 32u && tG <= (1u << 24)) G = tG;
   m.B = B; m.G = G;
   // Look-back of the entry guess.  Formats with the 7-bit-or-4-byte range field (8 bit Packed, byte-aligned Packed) kill a walk that
@@ -1203,8 +1204,8 @@ static int mono_prepare(const MonoHeader &mh, const uint8_t *dStream, uint8_t *d
   return HSRLE_OK;
 }
 
-// walk of every region, resolve round 1, gated records, decode: nothing here waits for the host
-static int mono_enqueue_first_try(const MonoHeader &mh, uint8_t *ws, const MonoPlan &m, MonoRun &run, hipStream_t st)
+// walk of every region, resolve round 1, gated records, decode (unless only the index is wanted): nothing here waits for the host
+static int mono_enqueue_first_try(const MonoHeader &mh, uint8_t *ws, const MonoPlan &m, MonoRun &run, hipStream_t st, bool decode = true)
 {
   if (g_idx[mh.codec](run.ia, 0, st) != hipSuccess || launch_resolve(m, ws, mh.p0, mh.U, 1u, st) != hipSuccess)
     return HSRLE_ERR_DEVICE;
@@ -1212,7 +1213,7 @@ static int mono_enqueue_first_try(const MonoHeader &mh, uint8_t *ws, const MonoP
   const hipError_t e = g_idx[mh.codec](run.ia, 1, st);
   run.ia.gate = nullptr;
   run.da.gate = run.ctrl;                                                // (the decode too: nothing to decode from records that were not written)
-  const hipError_t e2 = e != hipSuccess ? e : g_dec[mh.codec](run.da, st);
+  const hipError_t e2 = (e != hipSuccess || !decode) ? e : g_dec[mh.codec](run.da, st);
   run.da.gate = nullptr;
   if (e2 != hipSuccess)
     return HSRLE_ERR_DEVICE;
@@ -1227,8 +1228,11 @@ __global__ void k_mono_status(const uint32_t *__restrict__ ctrl, uint32_t *__res
 
 // dStream: 128-byte aligned, readable up to C + 64.  stats (optional): [0] regions, [1] repair rounds, [2] regions walked again.
 // Synchronises the stream (once when every guess holds; the repair loop reads the resolve pass's verdict per round).
+// recOut != nullptr: the persistent index (hsrle_mono_index_build_dev) -- the proven records go to recOut (m.nb records, cleared here first)
+// instead of the workspace, and nothing is decoded (dOut is not used).
 // Returns HSRLE_OK / HSRLE_ERR_FORMAT / HSRLE_ERR_DEVICE.
-static int mono_decode_dev(const MonoHeader &mh, const uint8_t *dStream, uint8_t *dOut, uint8_t *ws, const MonoPlan &m, uint32_t *stats, hipStream_t st)
+static int mono_decode_dev(const MonoHeader &mh, const uint8_t *dStream, uint8_t *dOut, uint8_t *ws, const MonoPlan &m, uint32_t *stats, hipStream_t st,
+                           uint32_t *recOut = nullptr)
 {
   MonoRun run;
   const int prc = mono_prepare(mh, dStream, dOut, ws, m, &run, st);
@@ -1236,6 +1240,16 @@ static int mono_decode_dev(const MonoHeader &mh, const uint8_t *dStream, uint8_t
     return prc;
   IndexArgs &ia = run.ia;
   uint32_t *const ctrl = run.ctrl;
+  const bool decode = recOut == nullptr;
+  if (!decode)
+  {
+    // (every dword of every record is written -- the ones a codec's state does not use as zeros -- so the index bytes depend on the stream alone)
+    ia.rec = recOut;
+    const uint64_t n16 = m.nb * kEntryRecDwords / 4u;
+    hipLaunchKernelGGL(k_mono_clear, dim3((uint32_t)((n16 + 255u) / 256u)), dim3(256), 0, st, (u32x4 *)recOut, n16);
+    if (hipGetLastError() != hipSuccess)
+      return HSRLE_ERR_DEVICE;
+  }
   if (!m.range7 && m.R >= 16384u && g_monoTune[2] == 0u)                  // (small streams: the pilot's launch + read costs more than a widened second try)
   {
     // formats whose junk walks do not die: does the short look-back find the chain on THIS stream?  A pilot over the first 128 regions
@@ -1252,7 +1266,7 @@ static int mono_decode_dev(const MonoHeader &mh, const uint8_t *dStream, uint8_t
   }
   uint32_t rounds = 0, rewalked = 0, roundTag = 1;
   uint32_t verdict[12] = { 0 };                                            // [0..3] the resolve pass's verdict, [8] the decode kernel's status
-  if (mono_enqueue_first_try(mh, ws, m, run, st) != HSRLE_OK ||
+  if (mono_enqueue_first_try(mh, ws, m, run, st, decode) != HSRLE_OK ||
       hipMemcpyAsync(verdict, ctrl, 36, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
     return HSRLE_ERR_DEVICE;
   if (verdict[0] == 0u)
@@ -1290,6 +1304,8 @@ static int mono_decode_dev(const MonoHeader &mh, const uint8_t *dStream, uint8_t
 
   // (the first try's decode lanes found zero records and left their error bits in the status word)
   ia.list = nullptr; ia.listCount = 0;
+  if (!decode)
+    return g_idx[mh.codec](ia, 1, st) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
   hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, st, ctrl + 8, 0u);
   if (g_idx[mh.codec](ia, 1, st) != hipSuccess || g_dec[mh.codec](run.da, st) != hipSuccess)
     return HSRLE_ERR_DEVICE;
@@ -1297,6 +1313,93 @@ static int mono_decode_dev(const MonoHeader &mh, const uint8_t *dStream, uint8_t
   if (hipMemcpyAsync(&status, ctrl + 8, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
     return HSRLE_ERR_DEVICE;
   return status == 0u ? HSRLE_OK : HSRLE_ERR_FORMAT;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// persistent index of a monolithic stream (hsrle_mono_index_*): the proven entry records of mono_decode_dev, kept behind a 64-byte header
+// in a buffer of the caller's, and the range decode that starts the block kernel's lanes from them.  Little endian, no pointers:
+//   [ 0] char     magic[8] = "HSRLEIDX"     [ 8] uint32_t version = 1     [12] uint32_t codec
+//   [16] uint32_t uncompressedSize           [20] uint32_t compressedSize  (both as in the stream's header)
+//   [24] uint32_t spacing                    [28] uint32_t recordCount = ceil(uncompressedSize / spacing)
+//   [32] uint32_t recordBytes = 96           [36] uint32_t reserved = 0
+//   [40] uint8_t  streamHead[16]  (the stream's first min(16, compressedSize) bytes, zeros behind)
+//   [56] uint64_t indexBytes = 64 + recordCount * recordBytes
+//   [64] records: entry record k (hsrle_common.hip.h kEntryRecDwords) = the decoder state at output position k * spacing; its stream
+//        position is relative to the stream's first byte, dwords a codec does not use are zero, and the high half of dword 4 holds
+//        a 16-bit tag of the 16 stream bytes at that position (the decoder reads only the low half of that dword)
+
+constexpr uint32_t kMonoIndexVersion = 1u;
+constexpr uint32_t kMonoIndexHeaderBytes = 64u;
+constexpr uint32_t kMonoIndexRecordBytes = 4u * kEntryRecDwords;
+constexpr uint32_t kRangeMismatch = 0x80000000u;    // range decode status word: the gate kernel's verdict (the decoder's error bits are the low ones)
+
+struct MonoIndexHeader
+{
+  char magic[8];
+  uint32_t version, codec, U, C, spacing, recordCount, recordBytes, reserved;
+  uint8_t head[16];
+  uint64_t indexBytes;
+};
+static_assert(sizeof(MonoIndexHeader) == kMonoIndexHeaderBytes, "index header is 64 bytes");
+static const char kMonoIndexMagic[8] = { 'H', 'S', 'R', 'L', 'E', 'I', 'D', 'X' };
+
+static bool valid_spacing(uint32_t spacing) { return spacing >= 128u && spacing <= (1u << 20) && (spacing % 128u) == 0u; }
+
+// the info a range decode is handed (or a header that was read) against itself: sizes, spacing, record count, and the stream head's own header
+static bool mono_index_info_ok(const hsrle_mono_index_info_t *info, MonoHeader *mh)
+{
+  if (info->version != kMonoIndexVersion || info->codec >= (uint32_t)kCodecCount || info->uncompressedSize == 0u || !valid_spacing(info->spacing))
+    return false;
+  const uint64_t n = ((uint64_t)info->uncompressedSize + info->spacing - 1u) / info->spacing;
+  if (info->recordCount != n || info->recordBytes != kMonoIndexRecordBytes || info->indexBytes != kMonoIndexHeaderBytes + n * kMonoIndexRecordBytes)
+    return false;
+  return mono_header((int)info->codec, info->streamHead, info->compressedSize, info->uncompressedSize, mh) && mh->U == info->uncompressedSize && mh->C == info->compressedSize;
+}
+
+// 16-bit tag of the (at most 16) stream bytes at position pos: what ties a record to the stream it was built from
+__device__ __forceinline__ uint32_t record_tag(const uint8_t *__restrict__ s, uint32_t C, uint32_t pos)
+{
+  uint32_t h = 0x811C9DC5u;
+#pragma unroll
+  for (uint32_t j = 0; j < 16u; j++)
+    h = (h ^ ((pos + j < C) ? (uint32_t)s[pos + j] : 0u)) * 0x01000193u;
+  return (h ^ (h >> 16)) & 0xFFFFu;
+}
+
+__global__ __launch_bounds__(256) void k_index_tags(const uint8_t *__restrict__ s, uint32_t C, uint32_t *__restrict__ rec, uint32_t n)
+{
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  uint32_t *const r = rec + (uint64_t)i * kEntryRecDwords;
+  r[4] = (r[4] & 0xFFFFu) | (record_tag(s, C, r[0]) << 16);
+}
+
+// range decode, in front of the block kernel: does the index belong to this stream?  Thread 0 compares the header's stream head with the
+// stream's first bytes, every thread one record's tag with the stream bytes at its position.  A mismatch sets kRangeMismatch in the status
+// word, which the block kernel takes as its gate (it then writes nothing).
+__global__ __launch_bounds__(256) void k_range_gate(const uint8_t *__restrict__ s, uint32_t C, u32x4 head, const uint32_t *__restrict__ rec, uint32_t first, uint32_t n,
+                                                    uint32_t *__restrict__ status)
+{
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  bool bad = false;
+  if (i == 0u)
+#pragma unroll
+    for (uint32_t j = 0; j < 16u; j++)
+      bad |= ((j < C) ? (uint32_t)s[j] : 0u) != ((head[j >> 2] >> (8u * (j & 3u))) & 0xFFu);
+  if (i < n)
+  {
+    const uint32_t *const r = rec + (uint64_t)(first + i) * kEntryRecDwords;
+    const uint32_t pos = r[0];
+    bad |= r[1] != 0u || pos >= C || r[5] != C - pos || (r[4] >> 16) != record_tag(s, C, pos);
+  }
+  if (bad) atomicOr(status, kRangeMismatch);
+}
+
+// the range decodes' one word for the caller
+__global__ void k_range_status(uint32_t *status)
+{
+  const uint32_t v = *status;
+  *status = (v & kRangeMismatch) != 0u ? (uint32_t)HSRLE_MONO_INDEX_MISMATCH : (v != 0u ? (uint32_t)HSRLE_MONO_MALFORMED : (uint32_t)HSRLE_MONO_DONE);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -2878,6 +2981,135 @@ int hsrle_decompress_mono_dev_async(int codec, const void *dStream, const uint8_
   if (hipGetLastError() != hipSuccess) return HSRLE_ERR_DEVICE;
   if (pUncompressedSize) *pUncompressedSize = mh.U;
   return HSRLE_OK;
+}
+
+uint64_t hsrle_mono_index_size(int codec, uint32_t uncompressedSize, uint32_t compressedSize, uint32_t spacing)
+{
+  if (codec < 0 || codec >= kCodecCount || uncompressedSize == 0 || compressedSize < 10u || (spacing != 0u && !valid_spacing(spacing))) return 0;
+  const MonoPlan m = plan_mono(codec, uncompressedSize, compressedSize, codec_header_size(codec), spacing);
+  return kMonoIndexHeaderBytes + m.nb * kMonoIndexRecordBytes;
+}
+
+uint64_t hsrle_mono_index_workspace_size(int codec, uint32_t uncompressedSize, uint32_t compressedSize, uint32_t spacing)
+{
+  if (codec < 0 || codec >= kCodecCount || uncompressedSize == 0 || compressedSize < 10u || (spacing != 0u && !valid_spacing(spacing))) return 0;
+  return plan_mono(codec, uncompressedSize, compressedSize, codec_header_size(codec), spacing).total + 16u;   // (+ 16: as hsrle_decompress_mono_workspace_size)
+}
+
+int hsrle_mono_index_build_dev(int codec, const void *dStream, uint32_t streamSize, uint32_t spacing, void *dIndex, uint64_t indexCapacity, void *dWorkspace,
+                               uint64_t workspaceSize, hsrle_mono_index_info_t *pInfo, void *stream)
+{
+  if (!dStream || !dIndex || !dWorkspace || codec < 0 || codec >= kCodecCount || streamSize < codec_header_size(codec) || ((uintptr_t)dStream & 127u) != 0u ||
+      ((uintptr_t)dIndex & 15u) != 0u || (spacing != 0u && !valid_spacing(spacing)))
+    return HSRLE_ERR_ARGUMENT;
+  mono_align_workspace(dWorkspace, workspaceSize);
+  if (!device_ok()) return HSRLE_ERR_DEVICE;
+  const hipStream_t st = (hipStream_t)stream;
+  uint8_t h16[16] = { 0 };
+  if (hipMemcpyAsync(h16, dStream, streamSize < 16u ? streamSize : 16u, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return HSRLE_ERR_DEVICE;
+  MonoHeader mh;
+  if (!mono_header(codec, h16, streamSize, 0xFFFFFFFFu, &mh))
+    return HSRLE_ERR_FORMAT;
+  const MonoPlan m = plan_mono(mh.codec, mh.U, mh.C, mh.p0, spacing);
+  if (workspaceSize < m.total) return HSRLE_ERR_CAPACITY;
+  const uint64_t indexBytes = kMonoIndexHeaderBytes + m.nb * kMonoIndexRecordBytes;
+  if (indexCapacity < indexBytes) return HSRLE_ERR_CAPACITY;
+  uint32_t *const rec = (uint32_t *)((uint8_t *)dIndex + kMonoIndexHeaderBytes);
+  // the walk, the proof, the repairs and the records pass of the monolithic decode, the records written behind the header; then the tags
+  int rc = mono_decode_dev(mh, (const uint8_t *)dStream, nullptr, (uint8_t *)dWorkspace, m, nullptr, st, rec);
+  if (rc != HSRLE_OK) return rc;
+  hipLaunchKernelGGL(k_index_tags, dim3((uint32_t)((m.nb + 255u) / 256u)), dim3(256), 0, st, (const uint8_t *)dStream, mh.C, rec, (uint32_t)m.nb);
+  if (hipGetLastError() != hipSuccess) return HSRLE_ERR_DEVICE;
+  MonoIndexHeader h;
+  memset(&h, 0, sizeof(h));
+  memcpy(h.magic, kMonoIndexMagic, 8);
+  h.version = kMonoIndexVersion; h.codec = (uint32_t)codec; h.U = mh.U; h.C = mh.C; h.spacing = m.B; h.recordCount = (uint32_t)m.nb; h.recordBytes = kMonoIndexRecordBytes;
+  for (uint32_t j = 0; j < 16u && j < mh.C; j++) h.head[j] = h16[j];
+  h.indexBytes = indexBytes;
+  if (hipMemcpyAsync(dIndex, &h, sizeof(h), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return HSRLE_ERR_DEVICE;
+  if (pInfo) rc = hsrle_mono_index_info_host(&h, sizeof(h) + m.nb * kMonoIndexRecordBytes, pInfo);
+  return rc;
+}
+
+int hsrle_mono_index_info_host(const void *pIndex, uint64_t size, hsrle_mono_index_info_t *pInfo)
+{
+  if (!pIndex || !pInfo) return HSRLE_ERR_ARGUMENT;
+  if (size < kMonoIndexHeaderBytes) return HSRLE_ERR_FORMAT;
+  MonoIndexHeader h;
+  memcpy(&h, pIndex, sizeof(h));
+  hsrle_mono_index_info_t info;
+  info.version = h.version; info.codec = h.codec; info.uncompressedSize = h.U; info.compressedSize = h.C;
+  info.spacing = h.spacing; info.recordCount = h.recordCount; info.recordBytes = h.recordBytes;
+  memcpy(info.streamHead, h.head, 16);
+  info.indexBytes = h.indexBytes;
+  MonoHeader mh;
+  if (memcmp(h.magic, kMonoIndexMagic, 8) != 0 || h.reserved != 0u || !mono_index_info_ok(&info, &mh) || size < info.indexBytes)
+    return HSRLE_ERR_FORMAT;
+  *pInfo = info;
+  return HSRLE_OK;
+}
+
+int hsrle_mono_decompress_range_dev_async(const void *dStream, const void *dIndex, const hsrle_mono_index_info_t *info, uint64_t offset, uint64_t length, void *dOut,
+                                          uint64_t outCapacity, uint32_t *dStatus, void *stream)
+{
+  if (!dStream || !dIndex || !info || !dOut || !dStatus || ((uintptr_t)dStream & 127u) != 0u || ((uintptr_t)dIndex & 15u) != 0u)
+    return HSRLE_ERR_ARGUMENT;
+  MonoHeader mh;
+  if (!mono_index_info_ok(info, &mh))
+    return HSRLE_ERR_FORMAT;
+  if (offset > info->uncompressedSize || length > info->uncompressedSize - offset || outCapacity < length)
+    return HSRLE_ERR_ARGUMENT;
+  if (length == 0u)
+    return HSRLE_OK;
+  if (!device_ok()) return HSRLE_ERR_DEVICE;
+  init_tables();
+  if (!g_dec[mh.codec])
+    return HSRLE_ERR_UNSUPPORTED;
+  const hipStream_t st = (hipStream_t)stream;
+  const uint32_t B = info->spacing, first = (uint32_t)(offset / B), n = (uint32_t)((offset + length - 1u) / B) - first + 1u;
+  const uint32_t *rec = (const uint32_t *)((const uint8_t *)dIndex + kMonoIndexHeaderBytes);
+  u32x4 head;
+  memcpy(&head, info->streamHead, 16);
+  hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, st, dStatus, 0u);
+  hipLaunchKernelGGL(k_range_gate, dim3((n + 255u) / 256u), dim3(256), 0, st, (const uint8_t *)dStream, mh.C, head, rec, first, n, dStatus);
+  if (hipGetLastError() != hipSuccess) return HSRLE_ERR_DEVICE;
+  // lanes first .. first + n - 1, each from its record; only [offset, offset + length) is stored, at dOut.  The status word is the gate: a mismatch
+  // stops every workgroup (a decode error seen by an early workgroup may stop later ones too -- the result is MALFORMED either way)
+  DecodeArgs da{ (const uint8_t *)dStream, nullptr, (const uint8_t *)dStream + mh.C + HSRLE_CONTAINER_TAIL_PAD, (uint8_t *)dOut, mh.U, B, first, n, dStatus };
+  da.entries = rec; da.entryBase = 0; da.gate = dStatus; da.gateWords = 1; da.winLo = offset; da.winHi = offset + length;
+  if (g_dec[mh.codec](da, st) != hipSuccess) return HSRLE_ERR_DEVICE;
+  hipLaunchKernelGGL(k_range_status, dim3(1), dim3(1), 0, st, dStatus);
+  return hipGetLastError() == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
+}
+
+int hsrle_decompress_range_dev_async(const void *dContainer, const hsrle_container_info_t *info, uint64_t offset, uint64_t length, void *dOut, uint64_t outCapacity,
+                                     uint32_t *dStatus, void *stream)
+{
+  if (!dContainer || !info || !dOut || !dStatus)
+    return HSRLE_ERR_ARGUMENT;
+  if (info->codec >= (uint32_t)kCodecCount || !valid_block_size(info->blockSize) || info->blockCount != block_count(info->uncompressedSize, info->blockSize))
+    return HSRLE_ERR_FORMAT;
+  if (offset > info->uncompressedSize || length > info->uncompressedSize - offset || outCapacity < length)
+    return HSRLE_ERR_ARGUMENT;
+  if (length == 0u)
+    return HSRLE_OK;
+  if (!device_ok()) return HSRLE_ERR_DEVICE;
+  init_tables();
+  if (!g_dec[info->codec])
+    return HSRLE_ERR_UNSUPPORTED;
+  const hipStream_t st = (hipStream_t)stream;
+  const uint32_t first = (uint32_t)(offset / info->blockSize), n = (uint32_t)((offset + length - 1u) / info->blockSize) - first + 1u;
+  const uint8_t *container = (const uint8_t *)dContainer;
+  const uint8_t *payload = container + HSRLE_CONTAINER_HEADER_SIZE + 8ull * ((uint64_t)info->blockCount + 1ull);
+  hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, st, dStatus, 0u);
+  DecodeArgs da{ payload, (const uint64_t *)(container + HSRLE_CONTAINER_HEADER_SIZE), payload + info->payloadSize + HSRLE_CONTAINER_TAIL_PAD,
+                 (uint8_t *)dOut, info->uncompressedSize, info->blockSize, first, n, dStatus };
+  da.winLo = offset; da.winHi = offset + length;
+  if (g_dec[info->codec](da, st) != hipSuccess) return HSRLE_ERR_DEVICE;
+  hipLaunchKernelGGL(k_range_status, dim3(1), dim3(1), 0, st, dStatus);
+  return hipGetLastError() == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
 }
 
 int hsrle_hash_blocks_dev_async(const void *dContainer, const hsrle_container_info_t *info, uint32_t firstBlock, uint32_t blockCount, uint64_t *dHashes, void *stream)

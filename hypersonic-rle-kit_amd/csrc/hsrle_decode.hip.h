@@ -214,15 +214,22 @@ __device__ __forceinline__ uint32_t bfi(uint32_t mask, uint32_t a, uint32_t b) {
 //   launchers use it for the codec ids whose encoders only write mode 0 (rle8_multi, rle8_packed_multi); a mode-1 block in such a
 //   container is reported as DEC_ERR_MODE.  The Single codec ids and the host-pointer drop-in functions (which look at the mode
 //   byte first, like rle8_decompress does) use the general kernel.
-template <int FAM, int S, int AL, int T, int R, int Q = T, bool SGL = true, bool ENT = true>
+template <int FAM, int S, int AL, int T, int R, int Q = T, bool SGL = true, bool ENT = true, bool WIN = false>
 __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict__ payload, const uint64_t *__restrict__ offsets,
                                                       const uint8_t *__restrict__ payloadEnd, uint8_t *__restrict__ out, uint64_t U,
                                                       uint32_t B, uint32_t firstBlock, uint32_t blockCount, uint32_t *__restrict__ status,
-                                                      const uint32_t *__restrict__ entries, uint32_t entryBase, const uint32_t *__restrict__ gate)
+                                                      const uint32_t *__restrict__ entries, uint32_t entryBase, const uint32_t *__restrict__ gate,
+                                                      uint32_t gateWords, uint64_t winLo, uint64_t winHi)
 {
   // gate != nullptr (monolithic streams, the decode enqueued behind the index passes without the host in between): the resolve pass left regions to repair or
-  // found the chain malformed -- the entry records were not written, so there is nothing to decode: dOut and the status word stay untouched
-  if (gate != nullptr && (gate[0] | gate[1]) != 0u) return;
+  // found the chain malformed -- the entry records were not written, so there is nothing to decode: dOut and the status word stay untouched.
+  // gateWords: how many words the gate has (2: the resolve pass's verdict; 1: the range decode's status word, set by its gate kernel)
+  if (gate != nullptr && (gate[0] | (gateWords > 1u ? gate[1] : 0u)) != 0u) return;
+  // WIN: the instantiation with an output window (range decode, launched with [winLo, winHi) other than [0, U)): output position p is stored at
+  // out + (p - winLo) iff winLo <= p < winHi; the lanes still decode their whole blocks.  A test per flushed chunk cost every kernel 12 .. 30 VGPRs
+  // (a wave per SIMD less for the 3 / 7 symbol list codecs), so the other launches take the instantiation without the window code.
+  if constexpr (!WIN) { winLo = 0ull; winHi = ~0ull; }
+  uint8_t *const outw = (uint8_t *)((uintptr_t)out - (uintptr_t)winLo);
   // entries != nullptr: lane b starts from entry record (b - entryBase) -- the decoder state at output position b * B of a stream that
   // lies somewhere in `payload` (ONE monolithic reference stream, or sub-block b of a container block; hsrle_index.hip.h writes the
   // records) -- instead of from the header of block stream b; everything behind the prologue is the same: a lane still produces the
@@ -1366,7 +1373,12 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
 #ifdef HSRLE_STAMPS
     tq0 = __builtin_readcyclecounter();
 #endif
-    HS_EXCHANGE(fi, chunks != 0u ? (base | chunks) : 0u, CPR)          // base is a multiple of 16 while chunks are pending (after the tail bytes it is not), chunks <= 8
+    // Output window (WIN): a row whose chunks of this round do not all lie inside [winLo, winHi) -- only the rows of the first and the last block of
+    // a range -- is flushed by its owner lane on its own (below), chunk by chunk and masked at the window's ends; its serving lanes see no chunks.  The
+    // rows inside the window take the cooperative flush, whose stores are unaligned then (outw + p: like the position-parallel encoders').
+    const uint64_t rowAt = (uint64_t)b * B + base;
+    const bool ownFlush = WIN && chunks != 0u && (rowAt < winLo || rowAt + (chunks << 4) > winHi);
+    HS_EXCHANGE(fi, (chunks != 0u && !ownFlush) ? (base | chunks) : 0u, CPR)   // base is a multiple of 16 while chunks are pending (after the tail bytes it is not), chunks <= 8
     HS_XSTAMP(tx3)
 #pragma unroll
     for (int h = 0; h < CPR; h += FH)                                  // FH row-groups at a time bounds the live registers
@@ -1393,16 +1405,39 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
 #endif
         if (fAt[k] != 0xFFFFFFFFu)
           // streaming store: the output is written once and never read here, keep it from evicting the compressed lines in L2
-          __builtin_nontemporal_store(fv[k], (u32x4_unaligned *)(out + (uint64_t)(wgFirst + (uint32_t)q * RPI + lane / CPR) * B + fAt[k]));
+          __builtin_nontemporal_store(fv[k], (u32x4_unaligned *)(outw + (uint64_t)(wgFirst + (uint32_t)q * RPI + lane / CPR) * B + fAt[k]));
       }
     }
     HS_XSTAMP(tx4)
+    if (WIN && ownFlush)
+    {
+#pragma unroll 1
+      for (uint32_t c = 0; c < chunks; c++)
+      {
+        const u32x4 v = lds_ld128(row + ((CAP != 0u ? ((base + c * 16u) & ((uint32_t)T - 1u)) : c * 16u) ^ tsw));
+        const uint64_t P = rowAt + c * 16u;
+        if (P >= winLo && P + 16u <= winHi)
+          __builtin_nontemporal_store(v, (u32x4_unaligned *)(outw + P));
+        else if (P + 16u > winLo && P < winHi)
+        {
+#pragma unroll 1
+          for (uint32_t j = 0; j < 16u; j++)
+          {
+            const uint32_t d = j < 4u ? v.x : (j < 8u ? v.y : (j < 12u ? v.z : v.w));   // (selects: no dynamically indexed vector, no scratch)
+            if (P + j >= winLo && P + j < winHi) outw[P + j] = (uint8_t)(d >> (8u * (j & 3u)));
+          }
+        }
+      }
+    }
     base += chunks << 4;
     if (tailNow)
     {
       const uint32_t at = CAP != 0u ? (base & ((uint32_t)T - 1u)) : (chunks << 4);   // (capped rounds: base is already behind the flushed chunks)
       for (uint32_t k = 0; k < (produced & 15u); k++)
-        out[(uint64_t)b * B + base + k] = row[(at ^ tsw) + k];
+      {
+        const uint64_t P = (uint64_t)b * B + base + k;
+        if (!WIN || (P >= winLo && P < winHi)) outw[P] = row[(at ^ tsw) + k];
+      }
       base = o;                                                        // written exactly once
     }
 

@@ -34,6 +34,8 @@ struct DecodeArgs
   const uint32_t *entries = nullptr; // lane b starts from entry record b - entryBase (hsrle_index.hip.h) instead of from a block stream header
   uint32_t entryBase = 0;
   const uint32_t *gate = nullptr;    // decode enqueued BEFORE the host has seen the index passes' verdict: gate[0] | gate[1] != 0 (regions to repair / malformed) -> the kernel returns at once
+  uint32_t gateWords = 2;            // words of the gate: 2 (the resolve pass's verdict) or 1 (the range decode's status word)
+  uint64_t winLo = 0, winHi = ~0ull; // output window: position p is stored at out + (p - winLo) iff winLo <= p < winHi (range decode); the lanes still decode whole blocks
 };
 
 // index passes over one monolithic stream (hsrle_index.hip.h)
@@ -160,13 +162,16 @@ void register_w128(DecodeLaunch *dec, EncodeLaunch *enc, IndexLaunch *idx, SubBl
 template <typename... A>
 constexpr int kernel_arity(void (*)(A...)) { return (int)sizeof...(A); }
 
+// a launch with an output window other than [0, U) (range decode) takes the kernel instantiation with the window code (k_decode_blocks WIN)
+inline bool windowed(const DecodeArgs &a) { return a.winLo != 0ull || a.winHi < a.U; }
+
 template <typename KERNEL>
 inline hipError_t launch_decode(KERNEL k, const DecodeArgs &a, hipStream_t st)
 {
   if (a.residentWorkgroups != nullptr)
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(a.residentWorkgroups, k, 64, 0);
   const uint32_t grid = (a.blockCount + 63u) / 64u;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(64), 0, st, a.payload, a.offsets, a.payloadEnd, a.out, a.U, a.B, a.firstBlock, a.blockCount, a.status, a.entries, a.entryBase, a.gate);
+  hipLaunchKernelGGL(k, dim3(grid), dim3(64), 0, st, a.payload, a.offsets, a.payloadEnd, a.out, a.U, a.B, a.firstBlock, a.blockCount, a.status, a.entries, a.entryBase, a.gate, a.gateWords, a.winLo, a.winHi);
   return hipGetLastError();
 }
 

@@ -43,6 +43,22 @@ class ContainerInfo(ctypes.Structure):
         return HEADER_SIZE + 8 * (self.blockCount + 1)
 
 
+class MonoIndexInfo(ctypes.Structure):
+    """hsrle_mono_index_info_t: the header of a persistent index of one monolithic stream."""
+
+    _fields_ = [
+        ("version", ctypes.c_uint32),
+        ("codec", ctypes.c_uint32),
+        ("uncompressedSize", ctypes.c_uint32),
+        ("compressedSize", ctypes.c_uint32),
+        ("spacing", ctypes.c_uint32),
+        ("recordCount", ctypes.c_uint32),
+        ("recordBytes", ctypes.c_uint32),
+        ("streamHead", ctypes.c_uint8 * 16),
+        ("indexBytes", ctypes.c_uint64),
+    ]
+
+
 _LIB = None
 
 
@@ -120,6 +136,18 @@ def _lib():
     L.hsrle_compress_mono_dev.argtypes = [ci, vp, u32, vp, u64, vp, u64, ctypes.POINTER(u32), ctypes.POINTER(u32), vp]
     L.hsrle_compress_mono_dev_async.restype = ci
     L.hsrle_compress_mono_dev_async.argtypes = [ci, vp, u32, vp, u64, vp, u64, vp, vp]
+    L.hsrle_mono_index_size.restype = u64
+    L.hsrle_mono_index_size.argtypes = [ci, u32, u32, u32]
+    L.hsrle_mono_index_workspace_size.restype = u64
+    L.hsrle_mono_index_workspace_size.argtypes = [ci, u32, u32, u32]
+    L.hsrle_mono_index_build_dev.restype = ci
+    L.hsrle_mono_index_build_dev.argtypes = [ci, vp, u32, u32, vp, u64, vp, u64, ctypes.POINTER(MonoIndexInfo), vp]
+    L.hsrle_mono_index_info_host.restype = ci
+    L.hsrle_mono_index_info_host.argtypes = [vp, u64, ctypes.POINTER(MonoIndexInfo)]
+    L.hsrle_mono_decompress_range_dev_async.restype = ci
+    L.hsrle_mono_decompress_range_dev_async.argtypes = [vp, vp, ctypes.POINTER(MonoIndexInfo), u64, u64, vp, u64, vp, vp]
+    L.hsrle_decompress_range_dev_async.restype = ci
+    L.hsrle_decompress_range_dev_async.argtypes = [vp, ctypes.POINTER(ContainerInfo), u64, u64, vp, u64, vp, vp]
     L.hsrle_mono_tuning.restype = None
     L.hsrle_mono_tuning.argtypes = [u32, u32, u32]
     L.hsrle_mono_encode_stats.restype = None
@@ -326,6 +354,71 @@ def mono_decompress_workspace_size(codec, usize, csize):
     return int(_lib().hsrle_decompress_mono_workspace_size(codec_id(codec), usize, csize))
 
 
+MONO_INDEX_MISMATCH = 3
+
+
+def mono_index_size(codec, usize, csize, spacing=0):
+    return int(_lib().hsrle_mono_index_size(codec_id(codec), usize, csize, spacing))
+
+
+def mono_index_build(codec, stream_tensor, spacing=0, index=None, workspace=None, stream_size=None):
+    """hsrle_mono_index_build_dev: the persistent entry-point index of ONE monolithic stream in device memory (128-byte aligned, >= 64 bytes
+    of slack behind it), one record per `spacing` output bytes (0 = the library's choice).  Synchronous.  Returns (index tensor trimmed to
+    its size, MonoIndexInfo); index.cpu() is a file that can be stored beside the stream and loaded again (mono_index_info)."""
+    import torch
+
+    _check_u8_cuda(stream_tensor, "stream")
+    head = stream_tensor[:8].cpu().numpy().tobytes()
+    usize, csize = int.from_bytes(head[:4], "little"), int.from_bytes(head[4:8], "little")
+    ssize = csize if stream_size is None else int(stream_size)
+    cid = codec_id(codec)
+    if index is None:
+        need = _lib().hsrle_mono_index_size(cid, usize, csize, spacing)
+        if need == 0:
+            raise HsrleError(ERR_ARGUMENT, "hsrle_mono_index_size")
+        index = torch.empty(need, dtype=torch.uint8, device=stream_tensor.device)
+    _check_u8_cuda(index, "index")
+    if workspace is None:
+        need = _lib().hsrle_mono_index_workspace_size(cid, usize, csize, spacing)
+        workspace = _scratch(max(need, 256), stream_tensor.device)
+    _check_u8_cuda(workspace, "workspace")
+    info = MonoIndexInfo()
+    rc = _lib().hsrle_mono_index_build_dev(cid, ctypes.c_void_p(stream_tensor.data_ptr()), ssize, spacing, ctypes.c_void_p(index.data_ptr()), index.numel(),
+                                           ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), ctypes.byref(info), _stream_ptr())
+    if rc != OK:
+        raise HsrleError(rc, "hsrle_mono_index_build_dev")
+    return index[: info.indexBytes], info
+
+
+def mono_index_info(index):
+    """Parse and validate an index header (hsrle_mono_index_info_host): host bytes, a CPU tensor or a CUDA tensor (its header is copied)."""
+    if hasattr(index, "is_cuda"):
+        b = index.cpu().numpy().tobytes() if index.is_cuda else index.numpy().tobytes()
+        size = index.numel()
+    else:
+        b = bytes(index)
+        size = len(b)
+    info = MonoIndexInfo()
+    rc = _lib().hsrle_mono_index_info_host(b, size, ctypes.byref(info))
+    if rc != OK:
+        raise HsrleError(rc, "hsrle_mono_index_info_host")
+    return info
+
+
+def mono_decompress_range_dev_async(stream_tensor, index, info, offset, length, dst, status, stream=None):
+    """hsrle_mono_decompress_range_dev_async: enqueue the decode of output bytes [offset, offset + length) of ONE monolithic stream into
+    dst[0, length), from its index (CUDA tensor) and `info` (MonoIndexInfo).  Nothing synchronises (can be captured in a HIP graph).  `status`
+    (CUDA uint8 tensor of >= 4 bytes, read as one little-endian uint32) holds MONO_DONE / MONO_MALFORMED / MONO_INDEX_MISMATCH once the stream has run."""
+    for t, what in ((stream_tensor, "stream"), (index, "index"), (dst, "dst"), (status, "status")):
+        _check_u8_cuda(t, what)
+    if status.numel() < 4:
+        raise TypeError("status must hold 4 bytes")
+    rc = _lib().hsrle_mono_decompress_range_dev_async(ctypes.c_void_p(stream_tensor.data_ptr()), ctypes.c_void_p(index.data_ptr()), ctypes.byref(info), offset, length,
+                                                      ctypes.c_void_p(dst.data_ptr()), dst.numel(), ctypes.c_void_p(status.data_ptr()), _stream_ptr(stream))
+    if rc != OK:
+        raise HsrleError(rc, "hsrle_mono_decompress_range_dev_async")
+
+
 def call_dropin(name, data, out_cap):
     """Call one of the rle.h-named exports directly, e.g. call_dropin("rle8_packed_multi_compress", data, cap)."""
     f = getattr(_lib(), name)
@@ -421,6 +514,19 @@ def decompress_async(container, info, dst, status=None, first_block=0, block_cou
                                                   ctypes.c_void_p(dst.data_ptr()), dst.numel(), sp, _stream_ptr(stream))
     if rc != OK:
         raise HsrleError(rc, "hsrle_decompress_blocks_dev_async")
+
+
+def decompress_range_dev_async(container, info, offset, length, dst, status, stream=None):
+    """hsrle_decompress_range_dev_async: enqueue the decode of output bytes [offset, offset + length) of a device container into dst[0, length)
+    (one lane per covering block).  `status` (CUDA uint8 tensor of >= 4 bytes) holds MONO_DONE / MONO_MALFORMED once the stream has run."""
+    for t, what in ((container, "container"), (dst, "dst"), (status, "status")):
+        _check_u8_cuda(t, what)
+    if status.numel() < 4:
+        raise TypeError("status must hold 4 bytes")
+    rc = _lib().hsrle_decompress_range_dev_async(ctypes.c_void_p(container.data_ptr()), ctypes.byref(info), offset, length, ctypes.c_void_p(dst.data_ptr()), dst.numel(),
+                                                 ctypes.c_void_p(status.data_ptr()), _stream_ptr(stream))
+    if rc != OK:
+        raise HsrleError(rc, "hsrle_decompress_range_dev_async")
 
 
 def hash_blocks(container, info, first_block=0, block_count=None):

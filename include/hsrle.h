@@ -240,6 +240,52 @@ int hsrle_decompress_mono_dev_async(int codec, const void *dStream, const uint8_
  * HSRLE_ERR_CAPACITY, it never writes out of bounds). */
 void hsrle_mono_tuning(uint32_t blockSize, uint32_t regionSize, uint32_t lookBack);
 
+/*
+ * Seekable monolithic streams: a persistent entry-point index beside the stream (a SIDECAR: the stream itself stays byte-identical to the
+ * reference's), and a decode of any byte range from it.
+ *
+ * The index of ONE monolithic stream is a 64-byte header and one entry record per `spacing` output bytes: the decoder state at that
+ * position, as the monolithic decode proves it (csrc/hsrle_capi.hip documents the layout).  Little endian, no pointers: the bytes copied
+ * to the host are a file that can be stored beside the stream and loaded again, into any buffer, for the stream at any 128-byte aligned
+ * address.  The same stream and spacing always give the same index bytes (whatever the tuning knobs, repair rounds or addresses).
+ * Records are 96 bytes: at spacing 256 the index is 37 % of the uncompressed size, at 4 KiB 2.3 %, at 64 KiB 0.15 %.
+ *   spacing: 0 = the library's choice (the monolithic decode's own lane size), else a multiple of 128 in [128, 1 MiB].
+ *   Every codec hsrle_decompress_mono_dev decodes, the 8 bit Single mode included (the records carry the Single flag and symbol).
+ */
+typedef struct hsrle_mono_index_info
+{
+  uint32_t version, codec;
+  uint32_t uncompressedSize, compressedSize;   /* as in the stream's header */
+  uint32_t spacing, recordCount, recordBytes;  /* recordCount = ceil(uncompressedSize / spacing), recordBytes = 96 */
+  uint8_t streamHead[16];                      /* the stream's first min(16, compressedSize) bytes, zeros behind */
+  uint64_t indexBytes;                         /* 64 + recordCount * recordBytes */
+} hsrle_mono_index_info_t;
+
+/* bytes of the index / of the build's device workspace; 0 for invalid arguments */
+uint64_t hsrle_mono_index_size(int codec, uint32_t uncompressedSize, uint32_t compressedSize, uint32_t spacing);
+uint64_t hsrle_mono_index_workspace_size(int codec, uint32_t uncompressedSize, uint32_t compressedSize, uint32_t spacing);
+/* Build the index of the stream at dStream (128-byte aligned, readable up to streamSize + 64) into dIndex (16-byte aligned, indexCapacity >=
+ * hsrle_mono_index_size()).  The walk, proof and repair rounds of hsrle_decompress_mono_dev without its decode.  SYNCHRONOUS: reads the stream
+ * header and the proof's verdict back, may repair.  pInfo (optional) receives the header.  HSRLE_ERR_FORMAT for a malformed stream,
+ * HSRLE_ERR_CAPACITY for a small index or workspace, HSRLE_ERR_ARGUMENT for a bad pointer, alignment or spacing. */
+int hsrle_mono_index_build_dev(int codec, const void *dStream, uint32_t streamSize, uint32_t spacing, void *dIndex, uint64_t indexCapacity, void *dWorkspace,
+                               uint64_t workspaceSize, hsrle_mono_index_info_t *pInfo, void *stream);
+/* Validate an index header in host memory (magic, version, codec, record count against the sizes and spacing, size): HSRLE_ERR_FORMAT if bad. */
+int hsrle_mono_index_info_host(const void *pIndex, uint64_t size, hsrle_mono_index_info_t *pInfo);
+/*
+ * Decode output bytes [offset, offset + length) of the stream into dOut[0, length) (any byte address; nothing outside it is written).  Only the
+ * decode lanes offset / spacing .. (offset + length - 1) / spacing run, each from its record.  ENQUEUE-ONLY: nothing here synchronises or reads
+ * device memory, a HIP graph can capture the call; the index was proven when it was built, so there is no NEEDS_REPAIR.
+ * dStream as for hsrle_decompress_mono_dev; dIndex (device, 16-byte aligned) the index, `info` its header (host).  length == 0: HSRLE_OK, nothing
+ * enqueued; offset + length > uncompressedSize or outCapacity < length: HSRLE_ERR_ARGUMENT, nothing enqueued.
+ * dStatus (device, 4 bytes) receives HSRLE_MONO_DONE, HSRLE_MONO_MALFORMED (decoder error bits) or HSRLE_MONO_INDEX_MISMATCH: the stream's first
+ * 16 bytes differ from the index's stream head (nothing is written then), or a record's tag of the stream bytes at its entry position does not
+ * match (a stale index whose header happens to be equal).  After MISMATCH or MALFORMED the contents of dOut[0, length) are unspecified.
+ */
+#define HSRLE_MONO_INDEX_MISMATCH 3
+int hsrle_mono_decompress_range_dev_async(const void *dStream, const void *dIndex, const hsrle_mono_index_info_t *info, uint64_t offset, uint64_t length,
+                                          void *dOut, uint64_t outCapacity, uint32_t *dStatus, void *stream);
+
 /* ---------------------------------------------------------------------------------------------------------- */
 /* 2. device-resident block container API                                                                      */
 
@@ -321,6 +367,15 @@ int hsrle_decompress_dev(const void *dContainer, uint64_t containerSize, void *d
  * (used by the multi-GPU sharding: every rank decodes its contiguous block range). */
 int hsrle_decompress_blocks_dev_async(const void *dContainer, const hsrle_container_info_t *info, uint32_t firstBlock, uint32_t blockCount,
                                       void *dOut, uint64_t outCapacity, uint32_t *dStatus, void *stream);
+
+/*
+ * Decode output bytes [offset, offset + length) of a container into dOut[0, length) (any byte address; nothing outside it is written): one lane
+ * per covering block, started from the block's header.  No parallelism inside a block: a range in one huge block is decoded from that
+ * block's start by one lane.  ENQUEUE-ONLY (graph-capturable).  length == 0: HSRLE_OK, nothing enqueued; offset + length > uncompressedSize or
+ * outCapacity < length: HSRLE_ERR_ARGUMENT, nothing enqueued.  dStatus (device, 4 bytes, required) receives HSRLE_MONO_DONE or HSRLE_MONO_MALFORMED.
+ */
+int hsrle_decompress_range_dev_async(const void *dContainer, const hsrle_container_info_t *info, uint64_t offset, uint64_t length, void *dOut,
+                                     uint64_t outCapacity, uint32_t *dStatus, void *stream);
 
 /*
  * Split decode: for containers with too few blocks to fill the GPU with one lane per block (one lane walks one block's packet chain:
