@@ -75,6 +75,7 @@ static WaveEncodeLaunch g_wenc[kCodecCount];
 static PpwLaunch g_ppwL[kCodecCount];               // ... and those of hsrle_encodeLp.hip.h (hsrle_encodeLpw.hip.h)
 static PpwLaunch g_ppwS[kCodecCount];               // ... and the codecs of hsrle_encodeSp.hip.h (hsrle_encodeSpw.hip.h), by codec id
 static PpwLaunch g_ppw[2];                         // ... for units of any length (hsrle_encode8pw.hip.h): rle8_multi, rle8_packed_multi
+static PpwLaunch g_ppwSM[kCodecCount];              // ... the chunk mode of hsrle_encodeSpw.hip.h (the chunks of one monolithic stream), by codec id: 42 codecs
 static PpLaunch g_pp[kCodecCount];                  // position-parallel encoders (hsrle_encode8p.hip.h)
 static std::once_flag g_tableOnce;
 
@@ -85,6 +86,7 @@ static void init_tables()
     register_pp8(g_pp);
     register_pp8w(g_ppw);
     register_ppSw(g_ppwS);
+    register_ppSwM(g_ppwSM);
     register_ppLw(g_ppwL);
     register_pp8s(g_pp);
     register_pp128(g_pp);
@@ -1604,14 +1606,24 @@ static thread_local uint32_t g_monoEncLast[4] = { 0, 0, 0, 0 };   // this thread
 struct MonoEncPlan
 {
   uint32_t G, pieces;
-  bool windowed;                                       // rle8_multi / rle8_packed_multi: chunks of any length by the windowed position-parallel encoder (hsrle_encode8pw.hip.h)
+  bool windowed;                                       // mono_chunk_mode_codec(): chunks of any length by the windowed position-parallel encoders (hsrle_encode8pw.hip.h, hsrle_encodeSpw.hip.h)
   uint64_t offCutPos, offCutSym, offFlags, offIdx, offStarts, offSyms, offSlotOff, offSizes, offOffsets, offL1, offL2, offL3, offCtrl, offSlots, total;
   uint64_t offGuess, offListOut, offRoll1, offRoll2;   // codecs with a move-to-front list: 8 words per chunk / per 64 / per 4096 chunks
   uint64_t offPick;                                    // 8 bit Single: the symbol pick's sums (k_single_pick_mono)
   uint64_t offJobs; uint32_t jobCap;                   // 8 bit Single: literal stretches noted by the chunk encoders for k_copy_jobs
 };
 
-static bool mono_windowed(int codec) { return (codec == 0 || codec == 1) && g_ppw[codec] != nullptr && kPpwMinBlocks != 0xFFFFFFFFu && knob_u32("HSRLE_PP", 0u) != 2u; }
+// the codecs whose encoder state at a cut is fixed by the cut itself (no list, or a one-symbol list = the cut's symbol): rle8_multi / rle8_packed_multi, the plain /
+// Packed codecs of 2 .. 8 byte symbols (ids 6 + 8 w + {0, 1, 4, 5}), the Short codecs with no list or a one-symbol list (54 + 8 w + {0, 1, 4, 5}, 50, 51)
+static bool mono_chunk_mode_codec(int codec)
+{
+  if (codec == HSRLE_RLE8_MULTI || codec == HSRLE_RLE8_PACKED_MULTI || codec == kShortBase8 || codec == kShortBase8 + 1) return true;
+  const int v = (codec >= 6 && codec < 46) ? (codec - 6) & 7 : ((codec >= kShortBaseW && codec < kGreedyBase) ? (codec - kShortBaseW) & 7 : -1);
+  return v == 0 || v == 1 || v == 4 || v == 5;
+}
+static PpwLaunch mono_ppw_launcher(int codec) { return !mono_chunk_mode_codec(codec) ? nullptr : (codec <= 1 ? g_ppw[codec] : g_ppwSM[codec]); }
+static uint32_t mono_ppw_state_words(int codec) { return codec <= 1 ? kPpwStateWords : kPpwSStateWords; }
+static bool mono_windowed(int codec) { return mono_ppw_launcher(codec) != nullptr && kPpwMinBlocks != 0xFFFFFFFFu && knob_u32("HSRLE_PP", 0u) != 2u; }
 
 static MonoEncPlan plan_mono_encode(uint32_t U, int codec, bool lists = true)
 {
@@ -1654,16 +1666,31 @@ static MonoEncPlan plan_mono_encode(uint32_t U, int codec, bool lists = true)
     m.offRoll1 = at; at += align_up(64ull * ((n + 1) / 64 + 1), 256);
     m.offRoll2 = at; at += align_up(64ull * ((n + 1) / 4096 + 1), 256);
   }
-  // (windowed: no staging slots -- the window states and records live there: 32 + 1 024 bytes per window, at most U / 4 096 + chunks windows)
+  // (windowed: no staging slots -- the window states and records live there: 32 (8 bit) / 64 + 1 024 bytes per window, at most U / 4 096 + chunks windows)
   const uint64_t windowsMax = ((uint64_t)U >> 12) + n + 1ull;
-  const uint64_t slotBytes = (uint64_t)U + ((uint64_t)U >> 7) + 256ull * (n + 2) + 4096ull, windowBytes = align_up(4ull * kPpwStateWords * windowsMax, 256) + 4ull * kPpwStride * windowsMax + 512ull;
+  const uint64_t slotBytes = (uint64_t)U + ((uint64_t)U >> 7) + 256ull * (n + 2) + 4096ull;
+  const uint64_t windowBytes = align_up(4ull * mono_ppw_state_words(codec) * windowsMax, 256) + 4ull * kPpwStride * windowsMax + 512ull;
   m.offSlots = at; at += align_up(m.windowed && windowBytes > slotBytes ? windowBytes : slotBytes, 256);
   m.total = at;
   return m;
 }
 
+// the enqueue-only encode's word for the caller (hsrle_compress_mono_dev_enqueue): the device-side twin of the synchronous checks behind the windowed encoders
+// (ctrl[0] chunks, [2..3] the stream's size, [5] a chunk that did not end on its boundary run)
+__global__ void k_mono_enc_status(const uint32_t *__restrict__ ctrl, uint32_t maxChunks, uint32_t *__restrict__ status, uint32_t *__restrict__ size)
+{
+  if (threadIdx.x != 0u) return;
+  const uint32_t chunks = ctrl[0], lo = ctrl[2], hi = ctrl[3], fail = ctrl[5];
+  const bool ok = chunks != 0u && chunks <= maxChunks && lo != 0u && hi == 0u && fail == 0u;
+  *status = ok ? (uint32_t)HSRLE_MONO_DONE : (uint32_t)HSRLE_MONO_ENCODE_FAILED;
+  if (size) *size = ok ? lo : 0u;
+}
+
 // dOut: capacity >= rle_compress_bounds(U).  Synchronises the stream twice (chunk count, stream size) -- the windowed encoders once, at the end.
-static int mono_encode_dev(int codec, const uint8_t *dIn, uint32_t U, uint8_t *dOut, uint8_t *ws, const MonoEncPlan &m, uint32_t *pSize, uint32_t *pChunks, hipStream_t st)
+// pSize == nullptr: the windowed encoders only, nothing synchronises; pChunks is then a DEVICE word for the stream's size, and dStatus (device, if not nullptr)
+// receives HSRLE_MONO_DONE / HSRLE_MONO_ENCODE_FAILED (the size word then says 0 on failure).
+static int mono_encode_dev(int codec, const uint8_t *dIn, uint32_t U, uint8_t *dOut, uint8_t *ws, const MonoEncPlan &m, uint32_t *pSize, uint32_t *pChunks, hipStream_t st,
+                           uint32_t *dStatus = nullptr)
 {
   init_tables();
   int S = 1, aligned = 0, listK = 0;
@@ -1710,30 +1737,37 @@ static int mono_encode_dev(int codec, const uint8_t *dIn, uint32_t U, uint8_t *d
     return HSRLE_ERR_DEVICE;
   hipLaunchKernelGGL(k_mono_scatter, dim3((m.pieces + 255u) / 256u), dim3(256), 0, st, (const uint64_t *)cutPos, (const uint64_t *)cutSym, (const uint32_t *)flags, (const uint64_t *)idx,
                      m.pieces, (uint64_t)U, starts, syms, slotOff, ctrl);
-  // rle8_multi / rle8_packed_multi: the windowed position-parallel encoder takes chunks of any length (hsrle_encode8pw.hip.h) -- no step bound, no staging slots
+  // the codecs whose state at a cut the cut fixes: the windowed position-parallel encoders take chunks of any length (hsrle_encode8pw.hip.h: rle8_multi /
+  // rle8_packed_multi; hsrle_encodeSpw.hip.h in its chunk mode: plain / Packed / Short with no list or a one-symbol list) -- no step bound, no staging slots, no lists
   const uint64_t windowsMax = ((uint64_t)U >> 12) + m.pieces + 1ull;
   const bool windowed = m.windowed && mono_windowed(codec);
   if (windowed)
   {
     // every piece may be a chunk: a wave per possible chunk (those behind the last one write a zero size), a wave per possible window -- nothing is read back
     // before the end
+    const PpwLaunch launch = mono_ppw_launcher(codec);
     PpwArgs pa{};
     pa.in = dIn; pa.U = U; pa.B = 0u; pa.nUnits = m.pieces + 1u; pa.starts = starts; pa.syms = syms; pa.count = ctrl; pa.sizes = sizes; pa.offsets = offsets; pa.payload = dOut + hs;
     pa.nWindows = (uint32_t)windowsMax;
     pa.states = (uint32_t *)(ws + m.offSlots);
-    pa.recs = (uint32_t *)(ws + m.offSlots + align_up(4ull * kPpwStateWords * windowsMax, 256));
-    if (g_ppw[codec](pa, 0, st) != hipSuccess || scan_sizes(sizes, pa.nUnits, offsets, ws, w, st) != hipSuccess || g_ppw[codec](pa, 1, st) != hipSuccess)
+    pa.recs = (uint32_t *)(ws + m.offSlots + align_up(4ull * mono_ppw_state_words(codec) * windowsMax, 256));
+    pa.fail = ctrl + 5;                                                   // (zeroed above)
+    g_monoEncLast[0] = g_monoEncLast[1] = g_monoEncLast[2] = g_monoEncLast[3] = 0u;   // (no list, no rounds)
+    if (launch(pa, 0, st) != hipSuccess || scan_sizes(sizes, pa.nUnits, offsets, ws, w, st) != hipSuccess || launch(pa, 1, st) != hipSuccess)
       return HSRLE_ERR_DEVICE;
     hipLaunchKernelGGL(k_mono_finish, dim3(1), dim3(64), 0, st, dOut, U, hs, (const uint64_t *)offsets, (const uint32_t *)ctrl, ctrl, 0u);
     if (pSize == nullptr)
     {
-      // hsrle_compress_mono_dev_async: the size stays on the device (the stream's own header holds it; pChunks, if given, is a DEVICE word that receives it too)
-      if (pChunks) hipLaunchKernelGGL(k_copy_word, dim3(1), dim3(1), 0, st, (const uint32_t *)(ctrl + 2), pChunks);
+      // enqueue only: the size stays on the device (the stream's own header holds it; pChunks, if given, is a DEVICE word that receives it too)
+      if (dStatus) hipLaunchKernelGGL(k_mono_enc_status, dim3(1), dim3(64), 0, st, (const uint32_t *)ctrl, m.pieces + 1u, dStatus, pChunks);
+      else if (pChunks) hipLaunchKernelGGL(k_copy_word, dim3(1), dim3(1), 0, st, (const uint32_t *)(ctrl + 2), pChunks);
       return hipGetLastError() == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
     }
-    uint32_t back[4] = { 0, 0, 0, 0 };                                    // chunks, -, stream size, error
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(back, ctrl, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    uint32_t back[6] = { 0, 0, 0, 0, 0, 0 };                              // chunks, -, stream size (2 words), -, a chunk that missed its boundary run
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(back, ctrl, 24, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
       return HSRLE_ERR_DEVICE;
+    if (back[5] != 0u)
+      return HSRLE_ERR_UNSUPPORTED;                                      // (never a stream with a hole: the drop-in functions then use one lane)
     if (back[0] == 0u || back[0] > m.pieces + 1u || back[3] != 0u || back[2] == 0u)
       return HSRLE_ERR_DEVICE;
     if (pChunks) *pChunks = back[0];
@@ -2920,9 +2954,24 @@ int hsrle_compress_mono_dev_async(int codec, const void *dIn, uint32_t inSize, v
   if (outCapacity < bounds32(inSize)) return HSRLE_ERR_CAPACITY;
   if (!device_ok()) return HSRLE_ERR_DEVICE;
   const MonoEncPlan m = plan_mono_encode(inSize, codec);
-  if (!m.windowed) return HSRLE_ERR_UNSUPPORTED;                          // (the other codecs' flows read chunk counts and list verdicts back)
+  if (codec > 1 || !m.windowed) return HSRLE_ERR_UNSUPPORTED;             // (the 8 bit pair only, as ever: the other codecs take hsrle_compress_mono_dev_enqueue)
   if (workspaceSize < m.total) return HSRLE_ERR_CAPACITY;
   return mono_encode_dev(codec, (const uint8_t *)dIn, inSize, (uint8_t *)dOut, (uint8_t *)dWorkspace, m, nullptr, dStreamSize, (hipStream_t)stream);
+}
+
+int hsrle_compress_mono_dev_enqueue(int codec, const void *dIn, uint32_t inSize, void *dOut, uint64_t outCapacity, void *dWorkspace, uint64_t workspaceSize,
+                                    uint32_t *dStreamSize, uint32_t *dStatus, void *stream)
+{
+  if (codec < 0 || codec >= kCodecCount) return HSRLE_ERR_ARGUMENT;
+  if (!mono_chunk_mode_codec(codec)) return HSRLE_ERR_UNSUPPORTED;        // (before the device: the codec set is a property of the library)
+  if (!dIn || !dOut || !dWorkspace || !dStatus || inSize == 0) return HSRLE_ERR_ARGUMENT;
+  if (inSize > (1u << 30)) return HSRLE_ERR_UNSUPPORTED;
+  if (outCapacity < bounds32(inSize)) return HSRLE_ERR_CAPACITY;
+  if (!device_ok()) return HSRLE_ERR_DEVICE;
+  const MonoEncPlan m = plan_mono_encode(inSize, codec);
+  if (!m.windowed) return HSRLE_ERR_UNSUPPORTED;                          // (experiment builds that force the old flow)
+  if (workspaceSize < m.total) return HSRLE_ERR_CAPACITY;
+  return mono_encode_dev(codec, (const uint8_t *)dIn, inSize, (uint8_t *)dOut, (uint8_t *)dWorkspace, m, nullptr, dStreamSize, (hipStream_t)stream, dStatus);
 }
 
 uint64_t hsrle_decompress_mono_workspace_size(int codec, uint32_t uncompressedSize, uint32_t compressedSize)

@@ -10,6 +10,11 @@
 // Pass 1 (k_encodeS_ppw_scan): one wave per block, window after window -> sizes[], a state record per window, a 32 bit record per stored run.
 // Pass 2 (k_encodeS_ppw_emit): one wave per window -> the packets of the runs that belong to it; the literal bytes of the window's first packet that lie in front of
 // the window go from the input straight to their place (hsrle_encode8pw.hip.h).
+// MONO = true: the units are the chunks of ONE monolithic stream (hsrle_mono_encode.hip.h), as hsrle_encode8pw.hip.h takes them with PpwArgs.B == 0.  A chunk
+// starts behind a run that every encoder state stores, so what crosses its left edge is known: lastRLE = the cut, the last stored symbol = the cut's symbol
+// (syms[] of k_mono_scatter) -- for the Short codecs with a one-symbol list that list too (storing a run sets it: rleX_Xsl_short.h:165-166, :255-258) -- and the
+// search resumes at the cut.  No header (k_mono_finish writes it), the last chunk alone ends the stream; the rules that look at the end of the input (match bits,
+// the byte-aligned extension, the end of the last run) look at nT, the bytes up to the input's end, and a chunk stores no run whose match stretch ends behind it.
 #pragma once
 
 #include "hsrle_encodeSp.hip.h"
@@ -26,8 +31,8 @@ struct PpSwCarry
   bool ended;
 };
 
-template <int FAM, int S, int AL, int MODE>
-__device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint32_t n, uint32_t w, PpSwCarry &cs, uint32_t pCar, uint32_t *__restrict__ st, uint32_t *__restrict__ myRecs,
+template <int FAM, int S, int AL, int MODE, bool MONO>
+__device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint32_t n, uint32_t nT, bool hasTerm, uint32_t w, PpSwCarry &cs, uint32_t pCar, uint32_t *__restrict__ st, uint32_t *__restrict__ myRecs,
                                             uint32_t unit, uint32_t unitSize, uint8_t *__restrict__ dst, PpShared<MODE != 0, true, FAM == LUT3 || FAM == SHORT3> &sh, const u32x4 (&x)[4],
                                             uint32_t recN, uint32_t rec0)
 {
@@ -44,7 +49,9 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
   constexpr bool R7 = TR::kRange7;
   constexpr uint32_t TERM = SH ? ((SH1 || SH3) ? 9u : 9u + SU) : (LUT ? 8u : (PK ? 5u : SU + 5u) + (R7 ? 4u : 5u));
   constexpr uint32_t TERM_END = SH ? ((SH1 || SH3) ? 7u : 8u) : (LUT ? 6u : TERM);
-  constexpr uint32_t HDR = 8u;
+  constexpr uint32_t HDR = MONO ? 0u : 8u;
+  const uint32_t nE = MONO ? nT : n;                   // (where the input ends: a chunk's match bits and runs may look behind the chunk)
+  const bool term = !MONO || hasTerm;
   const uint32_t lane = threadIdx.x;
   const uint32_t ws = w * kPpwWindow;
   const uint32_t base = lane * 64u;                    // (window relative)
@@ -76,8 +83,8 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
   if (lane == 63u)
   {
     const uint32_t bp = ws + kPpwWindow;
-    if (bp + 16u <= n) back0 = ld128(d + bp);
-    else if (bp < n) back0 = load16_edge(d, (int64_t)bp, (uint64_t)n);
+    if (bp + 16u <= nE) back0 = ld128(d + bp);
+    else if (bp < nE) back0 = load16_edge(d, (int64_t)bp, (uint64_t)nE);
   }
 #pragma unroll
   for (uint32_t j = 0; j < 4u; j++) lds_st128(sh.inb + kPpInPad + base + 16u * j, x[j]);
@@ -122,8 +129,8 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
       }
       m64 |= (uint64_t)zero_mask16(t[0], t[1], t[2], t[3]) << (16 * j);
     }
-    // position j matches only if j + S < n
-    const int64_t vb = (int64_t)n - (int64_t)SU - (int64_t)(ws + base);
+    // position j matches only if j + S < n (the input's end)
+    const int64_t vb = (int64_t)nE - (int64_t)SU - (int64_t)(ws + base);
     const uint32_t validBits = vb <= 0 ? 0u : (vb >= 64 ? 64u : (uint32_t)vb);
     m64 &= (validBits >= 64u) ? ~0ull : ((1ull << validBits) - 1ull);
     // lane 0: the match bits of the 8 positions in front of the window, in the top byte of a dword (what the lane in front would hand over)
@@ -138,7 +145,7 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
         const uint32_t j = i + SU;                                         // byte i of f8 against byte i + S of (f8, a8, b8)
         const uint32_t lhs = (uint32_t)(f8 >> (8u * i)) & 0xFFu;
         const uint32_t rhs = (j < 8u) ? (uint32_t)(f8 >> (8u * j)) & 0xFFu : ((j < 16u) ? (uint32_t)(a8 >> (8u * (j - 8u))) & 0xFFu : (uint32_t)(b8 >> (8u * (j - 16u))) & 0xFFu);
-        if (lhs == rhs && ws - 8u + i + SU < n) histM |= 1u << (24u + i);
+        if (lhs == rhs && ws - 8u + i + SU < nE) histM |= 1u << (24u + i);
       }
     }
     const uint32_t histC2 = histM & (histM << 1), histC4 = histC2 & (histC2 << 2);
@@ -175,7 +182,14 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
     else if constexpr (S == 4) histFull = histC4;
     else if constexpr (S == 6) histFull = histC4 & (histC2 << 4);
     else histFull = histC4 & (histC4 << 4);
-    const uint64_t cands = ends & shl_in(full, 1u, histFull);
+    uint64_t cands = ends & shl_in(full, 1u, histFull);
+    if constexpr (MONO)
+    {
+      // a chunk's runs: those whose match stretch ends in it (its boundary run's does, at n - S .. n - 1; the next stretch of S set bits cannot end before n)
+      const int64_t cb = (int64_t)n - (int64_t)(ws + base);
+      const uint32_t candBits = cb <= 0 ? 0u : (cb >= 64 ? 64u : (uint32_t)cb);
+      cands &= (candBits >= 64u) ? ~0ull : ((1ull << candBits) - 1ull);
+    }
     const uint32_t cnt = (uint32_t)__builtin_popcountll(cands);
     const uint32_t inclCnt = wave_scan_add(cnt);
     R = wave_lane(inclCnt, 63);
@@ -281,7 +295,7 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
           const uint32_t Leff = q - ps;
           const uint32_t whole = ((Leff + SU) / SU) * SU;
           const uint32_t eW = ps + whole;
-          e = (!AL && eW + SU <= n) ? q + SU : eW;
+          e = (!AL && eW + SU <= nE) ? q + SU : eW;
         }
       };
       if (geoKnown) { run_from(0u); outE = e; outEKnown = have && e != 0u; }
@@ -468,7 +482,7 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
       imgPos += wave_lane(incl, 63);
     }
     carL = wave_lane(outL, lastLane);
-    if (__ballot(k != 0 && e >= n) != 0ull) ended = true;
+    if (__ballot(k != 0 && e >= nE) != 0ull) ended = true;
   }
 
   if constexpr (MODE == 0)
@@ -482,13 +496,13 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
   {
     // ---- 3. header, terminator + trailing literals (the last window's packet) ----
     uint32_t imgSize = imgPos;
-    if (w == 0u && lane < 8u)
+    if (!MONO && w == 0u && lane < 8u)
     {
       const uint64_t h = (uint64_t)n | ((uint64_t)unitSize << 32);
       sh.img[lane] = (uint8_t)(h >> (8u * lane));
     }
     uint32_t tailSrc = 0, tailLen = 0;
-    if (lastWindow)
+    if (lastWindow && term)
     {
       const uint32_t kLit = ended ? 0u : n - carL;
       if (!ended)
@@ -572,8 +586,8 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
   }
 }
 
-// Pass 1: one wave per block
-template <int FAM, int S, int AL>
+// Pass 1: one wave per block (MONO: per chunk)
+template <int FAM, int S, int AL, bool MONO = false>
 __global__ __launch_bounds__(64) void k_encodeS_ppw_scan(PpwArgs a)
 {
   __shared__ PpShared<false, true, FAM == LUT3 || FAM == SHORT3> sh;
@@ -587,29 +601,67 @@ __global__ __launch_bounds__(64) void k_encodeS_ppw_scan(PpwArgs a)
   constexpr uint64_t SMASK = (S >= 8) ? ~0ull : ((1ull << (8 * (S & 7))) - 1ull);
   const uint32_t u = xcd_tile(blockIdx.x, gridDim.x);
   if (u >= a.nUnits) return;
-  const uint64_t at = (uint64_t)u * a.B;
-  const uint8_t *const d = a.in + at;
-  const uint32_t n = (uint32_t)((a.U - at) < (uint64_t)a.B ? (a.U - at) : (uint64_t)a.B);
-  const uint32_t slots = (a.B + kPpwWindow - 1u) / kPpwWindow, windows = (n + kPpwWindow - 1u) / kPpwWindow;
-  const uint64_t gw0 = (uint64_t)u * slots;
   PpSwCarry cs;
   cs.carL = 0u; cs.carE = 0u; cs.pos = 8u; cs.openStart = 0u; cs.carY = 0ull; cs.ended = false;
   cs.lA = 0ull; cs.lB = 0x7F7F7F7F7F7F7F7Full & SMASK; cs.lY = 0xFFFFFFFFFFFFFFFFull & SMASK;
+  const uint8_t *d;
+  uint32_t n, nT, slots;
+  uint64_t gw0;
+  bool hasTerm = true;
+  if constexpr (MONO)
+  {
+    static_assert(FAM == PLAIN || FAM == PACKED || FAM == SHORT0 || FAM == SHORT1, "chunk mode: the codecs whose state at a cut the cut fixes");
+    if (u >= a.count[0])
+    {
+      // (a unit behind the last chunk: its size is zero, and it marks the window slot nobody else owns)
+      if (threadIdx.x == 0u) { a.sizes[u] = 0u; a.states[(uint64_t)((uint32_t)(a.U >> 12) + u) * kPpwSStateWords + 12u] = kPpwEmpty; }
+      return;
+    }
+    const uint64_t at = a.starts[u], to = a.starts[u + 1u];
+    d = a.in + at;
+    n = (uint32_t)(to - at);
+    nT = (uint32_t)((a.U - at) < 0xFFFFFFFFull ? (a.U - at) : 0xFFFFFFFFull);
+    hasTerm = to >= a.U;
+    gw0 = (uint32_t)(at >> 12) + u;
+    slots = (uint32_t)(to >> 12) + u + 1u - (uint32_t)gw0;
+    cs.pos = 0u;
+    cs.carY = a.syms[u] & SMASK;                                            // (SHORT1: the one-symbol list is the last stored symbol)
+  }
+  else
+  {
+    const uint64_t at = (uint64_t)u * a.B;
+    d = a.in + at;
+    n = (uint32_t)((a.U - at) < (uint64_t)a.B ? (a.U - at) : (uint64_t)a.B);
+    nT = n;
+    slots = (a.B + kPpwWindow - 1u) / kPpwWindow;
+    gw0 = (uint64_t)u * slots;
+  }
+  const uint32_t windows = (n + kPpwWindow - 1u) / kPpwWindow;
   u32x4 x[4], xn[4];
-  ppw_load(d, n, 0u, x);
+  ppw_load(d, nT, 0u, x);
   for (uint32_t w = 0; w < windows; w++)
   {
-    if (w + 1u < windows) ppw_load(d, n, (w + 1u) * kPpwWindow, xn);
-    ppSw_window<FAM, S, AL, 0>(d, n, w, cs, 0u, a.states + (gw0 + w) * kPpwSStateWords, a.recs + (gw0 + w) * kPpwStride, u, 0u, nullptr, sh, x, kPpNoRecords, 0u);
+    if (w + 1u < windows) ppw_load(d, nT, (w + 1u) * kPpwWindow, xn);
+    ppSw_window<FAM, S, AL, 0, MONO>(d, n, nT, hasTerm, w, cs, 0u, a.states + (gw0 + w) * kPpwSStateWords, a.recs + (gw0 + w) * kPpwStride, u, 0u, nullptr, sh, x, kPpNoRecords, 0u);
     wave_sync();
 #pragma unroll
     for (int j = 0; j < 4; j++) x[j] = xn[j];
   }
-  if (threadIdx.x == 0u) a.sizes[u] = cs.pos + (cs.ended ? TERM_END : TERM + (n - cs.carL));
+  if constexpr (MONO)
+  {
+    if (threadIdx.x == 0u)
+    {
+      a.sizes[u] = cs.pos + (hasTerm ? (cs.ended ? TERM_END : TERM + (n - cs.carL)) : 0u);
+      if (!hasTerm && cs.carL != n) *a.fail = 1u;                           // (a chunk that did not end on its boundary run: the stream would be wrong -- say so)
+    }
+    for (uint32_t s = windows + threadIdx.x; s < slots; s += 64u) a.states[(gw0 + s) * kPpwSStateWords + 12u] = kPpwEmpty;
+  }
+  else if (threadIdx.x == 0u)
+    a.sizes[u] = cs.pos + (cs.ended ? TERM_END : TERM + (n - cs.carL));
 }
 
 // Pass 2: one wave per window
-template <int FAM, int S, int AL>
+template <int FAM, int S, int AL, bool MONO = false>
 __global__ __launch_bounds__(64) void k_encodeS_ppw_emit(PpwArgs a)
 {
   __shared__ PpShared<true, true, FAM == LUT3 || FAM == SHORT3> sh;
@@ -623,31 +675,58 @@ __global__ __launch_bounds__(64) void k_encodeS_ppw_emit(PpwArgs a)
   }
   const uint32_t gw = xcd_tile(blockIdx.x, gridDim.x);
   if (gw >= a.nWindows) return;
-  // (which block and window this is follows from the window's number: the state, the first records and the input are asked for together)
   const uint32_t *const st = a.states + (uint64_t)gw * kPpwSStateWords;
   const uint32_t *const myRecs = a.recs + (uint64_t)gw * kPpwStride;
-  const uint32_t slots = (a.B + kPpwWindow - 1u) / kPpwWindow;
-  const uint32_t u = gw / slots, w = gw - u * slots;
-  const uint64_t at = (uint64_t)u * a.B;
-  const uint8_t *const d = a.in + at;
-  const uint32_t n = (uint32_t)((a.U - at) < (uint64_t)a.B ? (a.U - at) : (uint64_t)a.B);
-  if (w * kPpwWindow >= n) return;                                       // (the last, short block: no such window)
-  const uint32_t sv = (threadIdx.x < kPpwSStateWords) ? st[threadIdx.x] : 0u;
-  const uint32_t rec0 = myRecs[threadIdx.x];
-  const uint32_t unitSize = a.sizes[u];
-  const uint64_t unitAt = a.offsets[u];
+  const uint8_t *d;
+  uint32_t n, nT, sv, rec0, recN, u, w, unitSize = 0;
+  uint64_t unitAt;
+  bool hasTerm = true;
   u32x4 x[4];
-  ppw_load(d, n, w * kPpwWindow, x);
-  const uint32_t recN = wave_lane(sv, 12);
+  if constexpr (MONO)
+  {
+    // chunks: the window's state record says which chunk and window it is (word 12 kPpwEmpty: no such window)
+    sv = (threadIdx.x < kPpwSStateWords) ? st[threadIdx.x] : 0u;
+    recN = wave_lane(sv, 12);
+    if (recN == kPpwEmpty) return;
+    u = wave_lane(sv, 13); w = wave_lane(sv, 14);
+    if (u >= a.count[0]) return;
+    rec0 = myRecs[threadIdx.x];
+    const uint64_t at = a.starts[u], to = a.starts[u + 1u];
+    d = a.in + at;
+    n = (uint32_t)(to - at);
+    nT = (uint32_t)((a.U - at) < 0xFFFFFFFFull ? (a.U - at) : 0xFFFFFFFFull);
+    hasTerm = to >= a.U;
+    unitAt = a.offsets[u];
+    ppw_load(d, nT, w * kPpwWindow, x);
+  }
+  else
+  {
+    // (which block and window this is follows from the window's number: the state, the first records and the input are asked for together)
+    const uint32_t slots = (a.B + kPpwWindow - 1u) / kPpwWindow;
+    u = gw / slots; w = gw - u * slots;
+    const uint64_t at = (uint64_t)u * a.B;
+    d = a.in + at;
+    n = (uint32_t)((a.U - at) < (uint64_t)a.B ? (a.U - at) : (uint64_t)a.B);
+    nT = n;
+    if (w * kPpwWindow >= n) return;                                     // (the last, short block: no such window)
+    sv = (threadIdx.x < kPpwSStateWords) ? st[threadIdx.x] : 0u;
+    rec0 = myRecs[threadIdx.x];
+    unitSize = a.sizes[u];
+    unitAt = a.offsets[u];
+    ppw_load(d, n, w * kPpwWindow, x);
+    recN = wave_lane(sv, 12);
+  }
   PpSwCarry cs;
   cs.pos = wave_lane(sv, 0); cs.carL = wave_lane(sv, 1); cs.openStart = wave_lane(sv, 2); cs.carE = wave_lane(sv, 3);
   cs.carY = (uint64_t)wave_lane(sv, 4) | ((uint64_t)wave_lane(sv, 5) << 32);
   cs.lA = (uint64_t)wave_lane(sv, 6) | ((uint64_t)wave_lane(sv, 7) << 32);
   cs.lB = (uint64_t)wave_lane(sv, 8) | ((uint64_t)wave_lane(sv, 9) << 32);
   cs.lY = (uint64_t)wave_lane(sv, 10) | ((uint64_t)wave_lane(sv, 11) << 32);
-  cs.ended = false;
+  // (chunks: a run stored in an earlier window may already reach the input's end -- its match stretch ends up to S bytes in front of that end, so in the
+  //  window in front of the last when the input ends 1 .. S - 1 bytes into a window: then lastRLE in front of the last window is the end)
+  cs.ended = MONO && cs.carL >= nT;
   wave_sync();
-  ppSw_window<FAM, S, AL, 1>(d, n, w, cs, wave_lane(sv, 15), nullptr, const_cast<uint32_t *>(myRecs), u, unitSize, a.payload + unitAt, sh, x, recN, rec0);
+  ppSw_window<FAM, S, AL, 1, MONO>(d, n, nT, hasTerm, w, cs, wave_lane(sv, 15), nullptr, const_cast<uint32_t *>(myRecs), u, unitSize, a.payload + unitAt, sh, x, recN, rec0);
 }
 
 } // namespace hsrle

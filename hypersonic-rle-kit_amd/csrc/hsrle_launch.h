@@ -115,12 +115,14 @@ struct PpwArgs
   uint32_t *states;               // [nWindows][kPpwStateWords]
   uint32_t *recs;                 // [nWindows][kPpwStride]
   uint32_t nWindows;
+  uint32_t *fail;                 // chunks of the 1 .. 8 byte symbol codecs (hsrle_encodeSpw.hip.h): set to 1 by a chunk that did not end on its boundary run
 };
 inline uint64_t ppw_scratch_bytes(uint64_t nWindows) { return nWindows * (4ull * kPpwStateWords + 4ull * kPpwStride) + 512ull; }
 
 typedef hipError_t (*PpwLaunch)(const PpwArgs &, int phase, hipStream_t);
 constexpr uint32_t kPpwLStateWords = 32u;                        // ... of the general LUT kernel's (hsrle_encodeLpw.hip.h): the list travels in the state record
 constexpr uint32_t kPpwSStateWords = 16u;                        // ... of the 1 .. 8 byte symbol codecs' windowed encoder (hsrle_encodeSpw.hip.h): more state crosses a window's edge
+                                                                 // (word 12 = the stored runs: kPpwEmpty there marks a slot with no such window)
 typedef hipError_t (*DecodeLaunch)(const DecodeArgs &, hipStream_t);
 typedef hipError_t (*EncodeLaunch)(const EncodeArgs &, hipStream_t);
 
@@ -148,6 +150,7 @@ void register_pp8(PpLaunch *pp);
 void register_pp8w(PpwLaunch *ppw);   // [0] rle8_multi, [1] rle8_packed_multi
 void register_ppLw(PpwLaunch *ppw);   // [codec id]: the codecs of hsrle_encodeLp.hip.h, blocks above 4 KiB
 void register_ppSw(PpwLaunch *ppw);   // [codec id]: the codecs of hsrle_encodeSp.hip.h, blocks above 4 KiB
+void register_ppSwM(PpwLaunch *ppw);  // [codec id]: their chunk mode (the chunks of one monolithic stream), the 42 codecs the cut fixes the state of
 void register_pp8s(PpLaunch *pp);
 void register_pp128(PpLaunch *pp);
 void register_ppL(PpLaunch *pp);

@@ -1,16 +1,17 @@
-// inst_ppSw.hip -- instantiations of the windowed position-parallel encoder of 1 .. 8 byte symbols (hsrle_encodeSpw.hip.h): the codecs of inst_ppS.hip, blocks above 4 KiB
+// inst_ppSw.hip -- instantiations of the windowed position-parallel encoder of 1 .. 8 byte symbols (hsrle_encodeSpw.hip.h): the codecs of inst_ppS.hip, blocks above 4 KiB;
+// and its chunk mode (MONO) for the chunks of one monolithic stream: the plain / Packed codecs and the Short codecs with no list or a one-symbol list
 #include "hsrle_launch.h"
 #include "hsrle_encodeSpw.hip.h"
 
 namespace hsrle {
 
-template <int FAM, int S, int AL>
+template <int FAM, int S, int AL, bool MONO = false>
 static hipError_t ppS_launch(const PpwArgs &a, int phase, hipStream_t st)
 {
   if (phase == 0)
-    hipLaunchKernelGGL((k_encodeS_ppw_scan<FAM, S, AL>), dim3(a.nUnits), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((k_encodeS_ppw_scan<FAM, S, AL, MONO>), dim3(a.nUnits), dim3(64), 0, st, a);
   else
-    hipLaunchKernelGGL((k_encodeS_ppw_emit<FAM, S, AL>), dim3(a.nWindows), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((k_encodeS_ppw_emit<FAM, S, AL, MONO>), dim3(a.nWindows), dim3(64), 0, st, a);
   return hipGetLastError();
 }
 
@@ -49,6 +50,27 @@ static void reg_short3(PpwLaunch *pp)
 {
   pp[54 + 8 * W + 2] = ppS_launch<SHORT3, S, 1>;
   pp[54 + 8 * W + 6] = ppS_launch<SHORT3, S, 0>;
+}
+
+// chunk mode: ids 6 + 8 * w + {0, 1, 4, 5}, 54 + 8 * w + {0, 1, 4, 5}, 50, 51 -- the encoder state at a cut is fixed by the cut (no list, or a list of one symbol)
+template <int S, int W>
+static void reg_mono(PpwLaunch *pp)
+{
+  pp[6 + 8 * W + 0] = ppS_launch<PLAIN, S, 1, true>;
+  pp[6 + 8 * W + 1] = ppS_launch<PACKED, S, 1, true>;
+  pp[6 + 8 * W + 4] = ppS_launch<PLAIN, S, 0, true>;
+  pp[6 + 8 * W + 5] = ppS_launch<PACKED, S, 0, true>;
+  pp[54 + 8 * W + 0] = ppS_launch<SHORT0, S, 1, true>;
+  pp[54 + 8 * W + 1] = ppS_launch<SHORT1, S, 1, true>;
+  pp[54 + 8 * W + 4] = ppS_launch<SHORT0, S, 0, true>;
+  pp[54 + 8 * W + 5] = ppS_launch<SHORT1, S, 0, true>;
+}
+
+void register_ppSwM(PpwLaunch *pp)
+{
+  pp[50] = ppS_launch<SHORT0, 1, 0, true>;      // rle8_multi_short
+  pp[51] = ppS_launch<SHORT1, 1, 0, true>;      // rle8_1symlut_short
+  reg_mono<2, 0>(pp); reg_mono<3, 1>(pp); reg_mono<4, 2>(pp); reg_mono<6, 3>(pp); reg_mono<8, 4>(pp);
 }
 
 void register_ppSw(PpwLaunch *pp)

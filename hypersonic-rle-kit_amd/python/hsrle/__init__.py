@@ -136,6 +136,8 @@ def _lib():
     L.hsrle_compress_mono_dev.argtypes = [ci, vp, u32, vp, u64, vp, u64, ctypes.POINTER(u32), ctypes.POINTER(u32), vp]
     L.hsrle_compress_mono_dev_async.restype = ci
     L.hsrle_compress_mono_dev_async.argtypes = [ci, vp, u32, vp, u64, vp, u64, vp, vp]
+    L.hsrle_compress_mono_dev_enqueue.restype = ci
+    L.hsrle_compress_mono_dev_enqueue.argtypes = [ci, vp, u32, vp, u64, vp, u64, vp, vp, vp]
     L.hsrle_mono_index_size.restype = u64
     L.hsrle_mono_index_size.argtypes = [ci, u32, u32, u32]
     L.hsrle_mono_index_workspace_size.restype = u64
@@ -290,15 +292,54 @@ def mono_compress_dev(codec, src, dst=None, workspace=None, return_chunks=False)
     return (dst[: size.value], chunks.value) if return_chunks else dst[: size.value]
 
 
+def _mono_encode_args(fn, src, dst, workspace, size_out, status=None):
+    """Every tensor of an enqueue-only encode checked before the call: a bad one raises HsrleError (ERR_ARGUMENT) here, not a fault on the device later.
+    src / dst / workspace: contiguous CUDA uint8 tensors; size_out / status: contiguous CUDA tensors of at least 4 bytes (any dtype)."""
+    import torch
+
+    def bad(what, need):
+        raise HsrleError(ERR_ARGUMENT, f"{fn}: {what} must be a contiguous CUDA {need}")
+
+    for t, what in ((src, "src"), (dst, "dst"), (workspace, "workspace")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+            bad(what, "uint8 tensor")
+    for t, what in ((size_out, "size_out"), (status, "status")):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.numel() * t.element_size() >= 4):
+            bad(what, "tensor of at least 4 bytes")
+
+
 def mono_compress_dev_async(codec, src, dst, workspace, size_out=None):
     """hsrle_compress_mono_dev_async (rle8_multi / rle8_packed_multi): enqueue the encode of ONE monolithic reference stream on the current stream; nothing
     synchronises (can be captured in a HIP graph).  dst (>= compress_bounds(n) bytes), workspace (>= hsrle_compress_mono_workspace_size) and size_out
     (uint32[1] or None) are CUDA tensors the caller owns; the stream's size is also in bytes 4 .. 7 of dst once the stream has run."""
-    _check_u8_cuda(src, "src")
+    _mono_encode_args("hsrle_compress_mono_dev_async", src, dst, workspace, size_out)
     rc = _lib().hsrle_compress_mono_dev_async(codec_id(codec), ctypes.c_void_p(src.data_ptr()), src.numel(), ctypes.c_void_p(dst.data_ptr()), dst.numel(),
                                               ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), ctypes.c_void_p(size_out.data_ptr() if size_out is not None else None), _stream_ptr())
     if rc != OK:
         raise HsrleError(rc, "hsrle_compress_mono_dev_async")
+
+
+MONO_ENCODE_FAILED = 4
+
+
+def mono_compress_dev_enqueue(codec, src, dst, workspace, status, size_out=None):
+    """hsrle_compress_mono_dev_enqueue: enqueue the encode of ONE monolithic reference stream on the current stream for the 44 codecs whose encoder state at a
+    cut the cut fixes (rle8_multi, rle8_packed_multi, plain / Packed of 16 .. 64 bit symbols, Short with no list or a one-symbol list); nothing synchronises (can
+    be captured in a HIP graph).  dst (>= compress_bounds(n) bytes) and workspace (>= hsrle_compress_mono_workspace_size) are uint8 CUDA tensors; status and
+    size_out (or None) are CUDA tensors of >= 4 bytes, read as one little-endian uint32: MONO_DONE / MONO_ENCODE_FAILED, and the stream's size (0 on failure),
+    once the stream has run."""
+    if status is None:
+        raise HsrleError(ERR_ARGUMENT, "hsrle_compress_mono_dev_enqueue: status is required")
+    _mono_encode_args("hsrle_compress_mono_dev_enqueue", src, dst, workspace, size_out, status)
+    rc = _lib().hsrle_compress_mono_dev_enqueue(codec_id(codec), ctypes.c_void_p(src.data_ptr()), src.numel(), ctypes.c_void_p(dst.data_ptr()), dst.numel(),
+                                                ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), ctypes.c_void_p(size_out.data_ptr() if size_out is not None else None),
+                                                ctypes.c_void_p(status.data_ptr()), _stream_ptr())
+    if rc != OK:
+        raise HsrleError(rc, "hsrle_compress_mono_dev_enqueue")
+
+
+def mono_compress_workspace_size(codec, n):
+    return int(_lib().hsrle_compress_mono_workspace_size(codec_id(codec), n))
 
 
 def mono_encode_stats():

@@ -212,10 +212,25 @@ void hsrle_mono_encode_stats(uint32_t stats[4]);
  * rle8_multi / rle8_packed_multi (round 6: their chunks go to the windowed position-parallel encoder, csrc/hsrle_encode8pw.hip.h -- no chunk count, no step bound
  * and no list verdict has to come back to the host): the same encode without the host in the loop.  Nothing here synchronises or reads device memory, a HIP
  * graph can capture the call.  The stream's size is in its own header (bytes 4 .. 7, as the reference writes it: src/rle8_extreme_cpu.h:330-338) and, if
- * dStreamSize (DEVICE, 4 bytes) is not NULL, there.  HSRLE_ERR_UNSUPPORTED for every other codec (use hsrle_compress_mono_dev).
+ * dStreamSize (DEVICE, 4 bytes) is not NULL, there.  HSRLE_ERR_UNSUPPORTED for every other codec: hsrle_compress_mono_dev_enqueue (below) takes the plain,
+ * Packed and Short codecs of wider symbols, with a device status word; hsrle_compress_mono_dev the rest.
  */
 int hsrle_compress_mono_dev_async(int codec, const void *dIn, uint32_t inSize, void *dOut, uint64_t outCapacity, void *dWorkspace, uint64_t workspaceSize, uint32_t *dStreamSize,
                                   void *stream);
+/*
+ * The enqueue-only encode of ONE monolithic reference stream for every codec whose encoder state at a cut is fixed by the cut itself: rle8_multi,
+ * rle8_packed_multi, the plain and Packed codecs of 16 .. 64 bit symbols (rle{16,24,32,48,64}_{sym,sym_packed,byte,byte_packed}), the Short codecs with no list or
+ * a one-symbol list (rle{16,24,32,48,64}_{sym,1symlut_sym,byte,1symlut_byte}_short, rle8_multi_short, rle8_1symlut_short) -- 44 codecs.  Their chunks go to the
+ * windowed position-parallel encoders in their chunk mode (csrc/hsrle_encode8pw.hip.h, csrc/hsrle_encodeSpw.hip.h).  Nothing here synchronises or reads device
+ * memory: a HIP graph can capture the call.  Every check happens on the host before anything is enqueued: HSRLE_ERR_UNSUPPORTED for the other codecs (use
+ * hsrle_compress_mono_dev), HSRLE_ERR_ARGUMENT / _CAPACITY / _DEVICE as for hsrle_compress_mono_dev.
+ * dStatus (DEVICE, 4 bytes, required) receives HSRLE_MONO_DONE (dOut holds the stream; its size is in its bytes 4 .. 7) or HSRLE_MONO_ENCODE_FAILED (the
+ * encode's own checks failed: dOut holds no stream).  dStreamSize (DEVICE, 4 bytes, may be NULL) receives the stream's size, 0 on failure.
+ * dOut capacity >= rle_compress_bounds(inSize); dWorkspace >= hsrle_compress_mono_workspace_size().
+ */
+#define HSRLE_MONO_ENCODE_FAILED 4
+int hsrle_compress_mono_dev_enqueue(int codec, const void *dIn, uint32_t inSize, void *dOut, uint64_t outCapacity, void *dWorkspace, uint64_t workspaceSize,
+                                    uint32_t *dStreamSize, uint32_t *dStatus, void *stream);
 int hsrle_decompress_mono_dev(int codec, const void *dStream, uint32_t streamSize, void *dOut, uint64_t outCapacity, void *dWorkspace, uint64_t workspaceSize,
                               uint32_t *pUncompressedSize, uint32_t *pStats, void *stream);
 /*
