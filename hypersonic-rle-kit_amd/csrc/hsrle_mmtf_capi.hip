@@ -1,0 +1,174 @@
+// hsrle_mmtf_capi.hip -- C ABI of the mmtf / bitmmtf transforms (include/hsrle.h section 5; reference: src/rle.h:420-438, src/mmtf.c, src/bit_mmtf.c).
+// The plan (segment length, chunk length, workspace layout) is made here on the host from the size alone; inst_mmtf.hip launches it.
+#include "../../include/hsrle.h"
+
+#include "hsrle_mmtf.h"
+
+#include <atomic>
+#include <math.h>
+#include <mutex>
+
+namespace hsrle {
+
+static std::atomic<uint32_t> g_mmtfSegmentRows{ 0 };
+
+static uint32_t isqrt32(uint32_t v)
+{
+  uint32_t r = (uint32_t)sqrt((double)v);
+  while ((uint64_t)r * r > v) r--;
+  while ((uint64_t)(r + 1u) * (r + 1u) <= v) r++;
+  return r;
+}
+static inline uint64_t min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
+
+constexpr uint32_t kMmtfLanes = 131072u;    // (segment, column) lanes that fill the device: 256 CUs x 8 resident waves x 64
+constexpr uint32_t kMmtfMinRows = 256u;     // a segment's state is 256 bytes per column: never more state than input
+constexpr uint32_t kBitChunks = 8192u, kBitMinChunk = 4096u;
+constexpr uint32_t kBitMaxChunks = 1u << 24;
+
+// With the library's own choice (tuning 0) the workspace is sized from BOUNDS of the segment / chunk count that grow with the size
+// (the counts themselves do not: the segment length is rounded), so hsrle_mmtf_workspace_size is monotone.
+static bool mmtf_plan(int transform, uint64_t size, MmtfPlan &p)
+{
+  if (transform < HSRLE_MMTF128 || transform > HSRLE_BITMMTF16 || size > 0xFFFFFFFFull)
+    return false;
+  const uint32_t tuning = g_mmtfSegmentRows.load();
+  p.size = (uint32_t)size;
+  if (transform <= HSRLE_MMTF256)
+  {
+    const uint32_t W = transform == HSRLE_MMTF128 ? 16u : 32u, target = kMmtfLanes / W;
+    p.W = W;
+    p.rows = p.size / W;
+    uint64_t segBound;
+    if (tuning != 0u)
+    {
+      p.R = tuning;
+      p.S = (uint32_t)(((uint64_t)p.rows + p.R - 1u) / p.R);
+      segBound = p.S;
+    }
+    else
+    {
+      const uint32_t root = isqrt32(p.rows);
+      uint32_t R = (p.rows + target - 1u) / target;
+      if (R < root) R = root;
+      if (R < kMmtfMinRows) R = kMmtfMinRows;
+      p.R = (R + 15u) & ~15u;   // whole 16-row tiles
+      p.S = (p.rows + p.R - 1u) / p.R;
+      segBound = min64(min64(target, (uint64_t)p.rows / kMmtfMinRows + 1u), (uint64_t)root + 3u);
+    }
+    const uint64_t groups = (segBound * W + 63u) / 64u;
+    p.offCounts = 0;
+    p.offTable = groups * 256u;
+    p.total = 256u + p.offTable + groups * 16384u;
+    return true;
+  }
+  const uint32_t E = transform == HSRLE_BITMMTF8 ? 1u : 2u, m = p.size & ~(E - 1u);
+  p.E = E;
+  uint64_t chunkBound;
+  uint64_t cb;
+  if (tuning != 0u)
+  {
+    cb = (uint64_t)tuning * E;
+    while (((uint64_t)m + cb - 1u) / cb > kBitMaxChunks) cb *= 2u;   // (a launch has a grid limit; the knob is for tests)
+    if (cb > 0x80000000ull) cb = 0x80000000ull;
+    chunkBound = ((uint64_t)m + cb - 1u) / cb;
+  }
+  else
+  {
+    cb = (((uint64_t)m + kBitChunks - 1u) / kBitChunks + 1023u) & ~1023ull;
+    if (cb < kBitMinChunk) cb = kBitMinChunk;
+    chunkBound = min64(kBitChunks, (uint64_t)m / kBitMinChunk + 1u);
+  }
+  p.chunkBytes = (uint32_t)cb;
+  p.chunks = (uint32_t)(((uint64_t)m + cb - 1u) / cb);
+  if (p.chunks == 0u) p.chunks = 1u;
+  if (chunkBound == 0u) chunkBound = 1u;
+  p.offVals = 0;
+  p.total = 256u + ((4u * chunkBound + 255u) & ~255ull);
+  return true;
+}
+
+// ---- staging of the host-pointer functions: per device, one call at a time on a device (as the other drop-in functions, hsrle_capi.hip) ----
+constexpr int kMmtfMaxDevices = 64;
+struct MmtfStaging
+{
+  std::mutex mu;
+  void *in = nullptr, *out = nullptr, *ws = nullptr;
+  uint64_t inSize = 0, outSize = 0, wsSize = 0;
+};
+static MmtfStaging g_mmtfStaging[kMmtfMaxDevices];
+
+static bool mmtf_grow(void **p, uint64_t *have, uint64_t need)
+{
+  if (*p && *have >= need) return true;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *have = 0;
+  if (hipMalloc(p, need) != hipSuccess) { (void)hipGetLastError(); return false; }
+  *have = need;
+  return true;
+}
+
+static uint32_t mmtf_dropin(int transform, int decode, const uint8_t *pIn, uint32_t inSize, uint8_t *pOut, uint32_t outSize)
+{
+  if (pIn == nullptr || pOut == nullptr || inSize == 0u || inSize > outSize)   // (mmtf.c does not look at the pointers; a NULL here is a 0, not a fault)
+    return 0;
+  int n = 0, d = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return 0; }
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMmtfMaxDevices) d = 0;
+  MmtfStaging &S = g_mmtfStaging[d];
+  std::lock_guard<std::mutex> lock(S.mu);
+  const uint64_t need = hsrle_mmtf_workspace_size(transform, inSize);
+  if (need == 0u || !mmtf_grow(&S.in, &S.inSize, (uint64_t)inSize + 64u) || !mmtf_grow(&S.out, &S.outSize, (uint64_t)inSize + 64u) || !mmtf_grow(&S.ws, &S.wsSize, need))
+    return 0;
+  if (hipMemcpy(S.in, pIn, inSize, hipMemcpyHostToDevice) != hipSuccess) return 0;
+  if (hsrle_mmtf_dev_async(transform, decode, S.in, inSize, S.out, S.ws, S.wsSize, nullptr) != HSRLE_OK) return 0;
+  if (hipMemcpy(pOut, S.out, inSize, hipMemcpyDeviceToHost) != hipSuccess) return 0;   // (synchronises the null stream)
+  return inSize;
+}
+
+}   // namespace hsrle
+
+using namespace hsrle;
+
+extern "C" {
+
+void hsrle_mmtf_tuning(uint32_t segmentRows) { g_mmtfSegmentRows.store(segmentRows); }
+
+uint64_t hsrle_mmtf_workspace_size(int transform, uint64_t size)
+{
+  MmtfPlan p;
+  return mmtf_plan(transform, size, p) ? p.total : 0u;
+}
+
+int hsrle_mmtf_dev_async(int transform, int decode, const void *dIn, uint64_t size, void *dOut, void *dWorkspace, uint64_t workspaceSize, void *stream)
+{
+  MmtfPlan p;
+  if (!mmtf_plan(transform, size, p))
+    return HSRLE_ERR_ARGUMENT;
+  if (size == 0u)
+    return HSRLE_OK;
+  if (dIn == nullptr || dOut == nullptr || dWorkspace == nullptr)
+    return HSRLE_ERR_ARGUMENT;
+  const uintptr_t a = (uintptr_t)dIn, b = (uintptr_t)dOut;
+  if (a < b + size && b < a + size)
+    return HSRLE_ERR_ARGUMENT;
+  if (workspaceSize < p.total)
+    return HSRLE_ERR_CAPACITY;
+  uint8_t *ws = (uint8_t *)(((uintptr_t)dWorkspace + 255u) & ~(uintptr_t)255u);
+  return mmtf_enqueue(p, decode != 0, (const uint8_t *)dIn, (uint8_t *)dOut, ws, (hipStream_t)stream) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
+}
+
+uint32_t mmtf_bounds(const uint32_t inSize) { return inSize; }       // mmtf.c
+uint32_t bitmmtf_bounds(const uint32_t inSize) { return inSize; }    // bit_mmtf.c
+
+#define HSRLE_MMTF_DROPIN(name, id) \
+  uint32_t name##_encode(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize) { return mmtf_dropin(id, 0, pIn, inSize, pOut, outSize); } \
+  uint32_t name##_decode(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize) { return mmtf_dropin(id, 1, pIn, inSize, pOut, outSize); }
+HSRLE_MMTF_DROPIN(mmtf128, HSRLE_MMTF128)
+HSRLE_MMTF_DROPIN(mmtf256, HSRLE_MMTF256)
+HSRLE_MMTF_DROPIN(bitmmtf8, HSRLE_BITMMTF8)
+HSRLE_MMTF_DROPIN(bitmmtf16, HSRLE_BITMMTF16)
+#undef HSRLE_MMTF_DROPIN
+
+}   // extern "C"

@@ -167,6 +167,15 @@ def _lib():
     L.hsrle_hash_blocks_dev_async.argtypes = [vp, ctypes.POINTER(ContainerInfo), u32, u32, vp, vp]
     L.hsrle_synth_dev_async.restype = ci
     L.hsrle_synth_dev_async.argtypes = [ci, ci, u64, vp, u64, vp]
+    L.hsrle_mmtf_workspace_size.restype = u64
+    L.hsrle_mmtf_workspace_size.argtypes = [ci, u64]
+    L.hsrle_mmtf_dev_async.restype = ci
+    L.hsrle_mmtf_dev_async.argtypes = [ci, ci, vp, u64, vp, vp, u64, vp]
+    L.hsrle_mmtf_tuning.restype = None
+    L.hsrle_mmtf_tuning.argtypes = [u32]
+    for nm in ("mmtf_bounds", "bitmmtf_bounds"):
+        getattr(L, nm).restype = u32
+        getattr(L, nm).argtypes = [u32]
     _LIB = L
     return L
 
@@ -725,3 +734,58 @@ def rle8m_bounds(sections, in_size):
     L = _lib()
     L.rle8m_compress_bounds.restype = ctypes.c_uint32
     return int(L.rle8m_compress_bounds(ctypes.c_uint32(sections), ctypes.c_uint32(in_size)))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the multi-move-to-front transforms (include/hsrle.h section 5; reference: src/rle.h:420-438)
+
+MMTF128, MMTF256, BITMMTF8, BITMMTF16 = 0, 1, 2, 3
+_MMTF_NAMES = ("mmtf128", "mmtf256", "bitmmtf8", "bitmmtf16")
+
+
+def mmtf_workspace_size(transform, size):
+    """hsrle_mmtf_workspace_size: bytes of device workspace of mmtf_dev (0: unknown transform, or a size above 2^32 - 1)."""
+    return int(_lib().hsrle_mmtf_workspace_size(transform, size))
+
+
+def mmtf_tuning(segment_rows=0):
+    """hsrle_mmtf_tuning: rows per segment (mmtf128 / mmtf256) / elements per chunk (bitmmtf decodes); 0 = the library's choice.  Process-global,
+    for tests; it changes mmtf_workspace_size."""
+    _lib().hsrle_mmtf_tuning(segment_rows)
+
+
+def mmtf_dev(transform, decode, src, dst, ws, stream=None):
+    """hsrle_mmtf_dev_async: enqueue one transform of the CUDA uint8 tensor `src` into dst[0, src.numel()) (any byte addresses, not overlapping).
+    Nothing synchronises (can be captured in a HIP graph); `ws` holds >= mmtf_workspace_size(transform, src.numel()) bytes, contents irrelevant."""
+    for t, what in ((src, "src"), (dst, "dst"), (ws, "ws")):
+        _check_u8_cuda(t, what)
+    if dst.numel() < src.numel():
+        raise TypeError("dst is shorter than src")
+    rc = _lib().hsrle_mmtf_dev_async(transform, 1 if decode else 0, ctypes.c_void_p(src.data_ptr()), src.numel(), ctypes.c_void_p(dst.data_ptr()),
+                                     ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(stream))
+    if rc != OK:
+        raise HsrleError(rc, "hsrle_mmtf_dev_async")
+
+
+def mmtf_bounds(n):
+    return int(_lib().mmtf_bounds(n))
+
+
+def bitmmtf_bounds(n):
+    return int(_lib().bitmmtf_bounds(n))
+
+
+def _mmtf_dropin(name):
+    def f(data, out_cap=None):
+        """The reference-named host-pointer function: returns (return value, output bytes[:return value])."""
+        data = bytes(data)
+        return call_dropin(name, data, len(data) if out_cap is None else out_cap)
+
+    f.__name__ = name
+    return f
+
+
+mmtf128_encode, mmtf128_decode = _mmtf_dropin("mmtf128_encode"), _mmtf_dropin("mmtf128_decode")
+mmtf256_encode, mmtf256_decode = _mmtf_dropin("mmtf256_encode"), _mmtf_dropin("mmtf256_decode")
+bitmmtf8_encode, bitmmtf8_decode = _mmtf_dropin("bitmmtf8_encode"), _mmtf_dropin("bitmmtf8_decode")
+bitmmtf16_encode, bitmmtf16_decode = _mmtf_dropin("bitmmtf16_encode"), _mmtf_dropin("bitmmtf16_decode")

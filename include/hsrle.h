@@ -586,6 +586,43 @@ typedef struct hsrle_rle8m_info { uint32_t compressedSize, uncompressedSize, sec
 int hsrle_rle8m_info_dev(const void *dStream, uint64_t streamSize, hsrle_rle8m_info_t *pInfo, void *stream);
 int hsrle_rle8m_decompress_dev_async(const void *dStream, const hsrle_rle8m_info_t *info, void *dOut, uint64_t outCapacity, uint32_t *dStatus, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------- */
+/* 5. the multi-move-to-front transforms (src/rle.h:420-438; src/mmtf.c, src/bit_mmtf.c): preconditioning steps that keep the size.     */
+/* mmtf128 / mmtf256: 16 / 32 interleaved byte columns, each with its own move-to-front list; encode writes ranks, decode symbols; the    */
+/* inSize % 16 (32) bytes behind the last whole row are looked up without an update.  bitmmtf8 / bitmmtf16: XOR with the previous byte /  */
+/* little-endian 16 bit word (an odd last byte of bitmmtf16 is copied).  Same names, arguments and return values as the reference: inSize */
+/* on success, 0 for inSize == 0, inSize > outSize, a NULL pointer or no usable device.  Host pointers, staged per device like section 1. */
+/* Still open of rle.h: rle8_mmtf128_* / rle8_mmtf256_* (RLE + MMTF + bit packing, rle.h:442-452) and rle8_sh_*.                           */
+uint32_t mmtf_bounds(const uint32_t inSize);
+uint32_t mmtf128_encode(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize);
+uint32_t mmtf128_decode(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize);
+uint32_t mmtf256_encode(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize);
+uint32_t mmtf256_decode(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize);
+uint32_t bitmmtf_bounds(const uint32_t inSize);
+uint32_t bitmmtf8_encode(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize);
+uint32_t bitmmtf8_decode(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize);
+uint32_t bitmmtf16_encode(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize);
+uint32_t bitmmtf16_decode(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize);
+
+/*
+ * The same, device resident and ENQUEUE-ONLY: nothing here allocates, synchronises or reads device memory, a HIP graph can capture the call, and it
+ * composes with hsrle_compress_dev_async / hsrle_decompress_dev_async on one stream.  dIn / dOut at any byte address, not overlapping; exactly `size`
+ * bytes are written.  dWorkspace >= hsrle_mmtf_workspace_size(transform, size) bytes at any address, its contents do not matter.  The move-to-front
+ * transforms cut the rows into segments (a lane per segment and column; csrc/hsrle_mmtf.hip.h) and keep 256 bytes of state per segment and column in
+ * the workspace: at most size / 8 + 1 MiB.  HSRLE_ERR_ARGUMENT: NULL pointer, unknown transform, size > 2^32 - 1, overlapping buffers;
+ * HSRLE_ERR_CAPACITY: short workspace; size == 0: HSRLE_OK, nothing is launched.  hsrle_mmtf_workspace_size: 0 for an unknown transform or such a size.
+ * hsrle_mmtf_tuning: rows per segment of mmtf128 / mmtf256 and elements per chunk of the bitmmtf decodes (the prefix XOR is a reduction per chunk, a
+ * scan of the chunk values and an apply pass); 0 = the library's choice.  Any value gives the same bytes.  PROCESS-GLOBAL and meant for tests, like
+ * hsrle_mono_tuning: it changes the workspace size.
+ */
+#define HSRLE_MMTF128 0
+#define HSRLE_MMTF256 1
+#define HSRLE_BITMMTF8 2
+#define HSRLE_BITMMTF16 3
+uint64_t hsrle_mmtf_workspace_size(int transform, uint64_t size);
+int hsrle_mmtf_dev_async(int transform, int decode, const void *dIn, uint64_t size, void *dOut, void *dWorkspace, uint64_t workspaceSize, void *stream);
+void hsrle_mmtf_tuning(uint32_t segmentRows);
+
 int hsrle_kernel_waves_per_cu(int codec, int decode);
 const char *hsrle_version(void);
 
