@@ -1,5 +1,6 @@
 // hsrle_capi.hip -- the C ABI of libhsrle_hip.so (include/hsrle.h): drop-in rle.h entry points, the device-resident
 // block container API, container assembly kernels (size scan + slot compaction) and the synthetic workload generator.
+// What a codec id means is said once, in hsrle_codecs.h: nothing here compares an id with a number.
 //
 // Host code here is plain C-style C++ behind `extern "C"`; no torch types, no CPU codec.  If no HIP device is usable
 // every entry point fails loudly (0 / HSRLE_ERR_DEVICE) -- there is no fallback path.
@@ -25,47 +26,6 @@ namespace hsrle { constexpr uint64_t kTicketBytes = 256; }   // (scratch behind 
 
 namespace hsrle {
 
-// ------------------------------------------------------------------------------------------------------------------
-// codec table (names follow the reference: src/rle.h, src/codec_funcs.h:270-410)
-
-static const char *const kCodecNames[kCodecCount] = {
-  "rle8_multi", "rle8_packed_multi", "rle8_3symlut", "rle8_7symlut", "rle8_single", "rle8_packed_single",
-  "rle16_sym", "rle16_sym_packed", "rle16_3symlut_sym", "rle16_7symlut_sym", "rle16_byte", "rle16_byte_packed", "rle16_3symlut_byte", "rle16_7symlut_byte",
-  "rle24_sym", "rle24_sym_packed", "rle24_3symlut_sym", "rle24_7symlut_sym", "rle24_byte", "rle24_byte_packed", "rle24_3symlut_byte", "rle24_7symlut_byte",
-  "rle32_sym", "rle32_sym_packed", "rle32_3symlut_sym", "rle32_7symlut_sym", "rle32_byte", "rle32_byte_packed", "rle32_3symlut_byte", "rle32_7symlut_byte",
-  "rle48_sym", "rle48_sym_packed", "rle48_3symlut_sym", "rle48_7symlut_sym", "rle48_byte", "rle48_byte_packed", "rle48_3symlut_byte", "rle48_7symlut_byte",
-  "rle64_sym", "rle64_sym_packed", "rle64_3symlut_sym", "rle64_7symlut_sym", "rle64_byte", "rle64_byte_packed", "rle64_3symlut_byte", "rle64_7symlut_byte",
-  "rle128_sym", "rle128_sym_packed", "rle128_byte", "rle128_byte_packed",
-  // Short family (reference: src/rle.h:202-348, src/codec_funcs.h:283-388)
-  "rle8_multi_short", "rle8_1symlut_short", "rle8_3symlut_short", "rle8_7symlut_short",
-  "rle16_sym_short", "rle16_1symlut_sym_short", "rle16_3symlut_sym_short", "rle16_7symlut_sym_short", "rle16_byte_short", "rle16_1symlut_byte_short", "rle16_3symlut_byte_short", "rle16_7symlut_byte_short",
-  "rle24_sym_short", "rle24_1symlut_sym_short", "rle24_3symlut_sym_short", "rle24_7symlut_sym_short", "rle24_byte_short", "rle24_1symlut_byte_short", "rle24_3symlut_byte_short", "rle24_7symlut_byte_short",
-  "rle32_sym_short", "rle32_1symlut_sym_short", "rle32_3symlut_sym_short", "rle32_7symlut_sym_short", "rle32_byte_short", "rle32_1symlut_byte_short", "rle32_3symlut_byte_short", "rle32_7symlut_byte_short",
-  "rle48_sym_short", "rle48_1symlut_sym_short", "rle48_3symlut_sym_short", "rle48_7symlut_sym_short", "rle48_byte_short", "rle48_1symlut_byte_short", "rle48_3symlut_byte_short", "rle48_7symlut_byte_short",
-  "rle64_sym_short", "rle64_1symlut_sym_short", "rle64_3symlut_sym_short", "rle64_7symlut_sym_short", "rle64_byte_short", "rle64_1symlut_byte_short", "rle64_3symlut_byte_short", "rle64_7symlut_byte_short",
-  // Greedy encoders (reference: src/rle.h:398-416); the decode side is the Short decoder of the same grammar
-  "rle16_1symlut_byte_short_greedy", "rle16_3symlut_byte_short_greedy", "rle16_7symlut_byte_short_greedy",
-  "rle24_1symlut_byte_short_greedy", "rle24_3symlut_byte_short_greedy", "rle24_7symlut_byte_short_greedy",
-  "rle32_1symlut_byte_short_greedy", "rle32_3symlut_byte_short_greedy", "rle32_7symlut_byte_short_greedy",
-  "rle48_1symlut_byte_short_greedy", "rle48_3symlut_byte_short_greedy", "rle48_7symlut_byte_short_greedy",
-  "rle64_1symlut_byte_short_greedy", "rle64_3symlut_byte_short_greedy", "rle64_7symlut_byte_short_greedy",
-  "rle8_single_short",
-};
-
-static inline bool codec_is_lut(int c) { return c == 2 || c == 3 || (c >= 6 && c < 46 && (((c - 6) & 3) >= 2)) || c >= kShortBase8; }   // 8-byte stream header
-static inline int codec_symbol_bytes(int c)
-{
-  static const int widths[5] = { 2, 3, 4, 6, 8 };
-  if (c < 6) return 1;
-  if (c < 46) return widths[(c - 6) >> 3];
-  if (c < 50) return 16;
-  if (c < kShortBaseW) return 1;
-  if (c < kGreedyBase) return widths[(c - kShortBaseW) >> 3];
-  if (c < kSingleShort) return widths[(c - kGreedyBase) / 3];
-  return 1;
-}
-static inline uint32_t codec_header_size(int c) { return (c < 6 && !codec_is_lut(c)) ? 9u : 8u; }
-
 static DecodeLaunch g_dec[kCodecCount];
 static EncodeLaunch g_enc[kCodecCount];
 static IndexLaunch g_idx[kCodecCount];
@@ -74,7 +34,7 @@ static MonoEncodeLaunch g_menc[kCodecCount];
 static WaveEncodeLaunch g_wenc[kCodecCount];
 static PpwLaunch g_ppwL[kCodecCount];               // ... and those of hsrle_encodeLp.hip.h (hsrle_encodeLpw.hip.h)
 static PpwLaunch g_ppwS[kCodecCount];               // ... and the codecs of hsrle_encodeSp.hip.h (hsrle_encodeSpw.hip.h), by codec id
-static PpwLaunch g_ppw[2];                         // ... for units of any length (hsrle_encode8pw.hip.h): rle8_multi, rle8_packed_multi
+static PpwLaunch g_ppw[kCodecCount];               // ... for units of any length (hsrle_encode8pw.hip.h), by codec id: rle8_multi, rle8_packed_multi
 static PpwLaunch g_ppwSM[kCodecCount];              // ... the chunk mode of hsrle_encodeSpw.hip.h (the chunks of one monolithic stream), by codec id: 42 codecs
 static PpLaunch g_pp[kCodecCount];                  // position-parallel encoders (hsrle_encode8p.hip.h)
 static std::once_flag g_tableOnce;
@@ -531,7 +491,6 @@ static uint32_t encode_chunk_blocks()
 constexpr uint32_t kSplitEncodeBelow = 131072u;   // blocks: from here on one lane per block fills the device
 constexpr uint32_t kSplitPieces = 4u, kSplitPiecesMax = 8u;             // (the workspace is planned for the larger number: split_pieces())
 static bool split_encode_applies(int codec, uint64_t nBlocks, uint32_t B);
-static bool split_codec_small(int codec);
 
 struct Workspace
 {
@@ -542,7 +501,7 @@ struct Workspace
 };
 
 // splitSmall: reserve the split-encode regions for blocks of 1 .. 4 KiB too (the codecs without a run list encoder -- 8 bit Single, 128 bit --
-// take the split encode there: split_codec_small(); hsrle_compress_workspace_size_codec)
+// take the split encode there: hsrle_codecs.h split_small(); hsrle_compress_workspace_size_codec)
 static Workspace plan_workspace(uint64_t U, uint32_t B, bool splitSmall = false, bool noSplit = false)
 {
   Workspace w;
@@ -662,8 +621,8 @@ static bool pp_applies(int codec, uint32_t nBlocks, uint32_t B)
 #endif
 constexpr uint32_t kPpwMinBlocks = HSRLE_PPW_MIN_BLOCKS;   // (A/B builds: 0xFFFFFFFF = never, also for the monolithic streams)
 // words of a window's state record: the 8 bit pair 8, the codecs of hsrle_encodeSp.hip.h 16, those of hsrle_encodeLp.hip.h (the list travels with it) 32
-static uint32_t ppw_state_words(int codec) { return codec <= 1 ? kPpwStateWords : (g_ppwL[codec] ? kPpwLStateWords : kPpwSStateWords); }
-static PpwLaunch ppw_launcher(int codec) { return (codec < 0 || codec >= kCodecCount) ? nullptr : ((codec <= 1) ? g_ppw[codec] : (g_ppwL[codec] ? g_ppwL[codec] : g_ppwS[codec])); }
+static uint32_t ppw_state_words(int codec) { return g_ppw[codec] ? kPpwStateWords : (g_ppwL[codec] ? kPpwLStateWords : kPpwSStateWords); }
+static PpwLaunch ppw_launcher(int codec) { return (codec < 0 || codec >= kCodecCount) ? nullptr : (g_ppw[codec] ? g_ppw[codec] : (g_ppwL[codec] ? g_ppwL[codec] : g_ppwS[codec])); }
 // (the plain / Packed codecs write 8 or 32 bit fields whatever the block size; the LUT / Short forms choose their field widths -- and the reference its penalties, with
 //  thresholds of 0xFFFFF: rleX_Xsl.h:130, rleX_Xsl_short.h:178 -- by the values: below 1 MiB per block no count or range gets there and "every run is stored" holds)
 constexpr uint32_t kPpwListMaxBlock = (1u << 20) - 128u;
@@ -671,8 +630,7 @@ static bool ppw_applies(int codec, uint32_t nBlocks, uint32_t B)
 {
   static const uint32_t force = knob_u32("HSRLE_PP", 0u);
   if (!ppw_launcher(codec) || B <= kPpMaxBlock || force == 2u) return false;
-  const bool anyBlock = codec <= 1 || (codec >= 6 && codec < 46 && ((codec - 6) & 2) == 0);                   // 8 bit multi, plain / Packed of 2 .. 8 byte symbols
-  if (!anyBlock && B > kPpwListMaxBlock) return false;
+  if (!any_block_windowed(kCodecs[codec]) && B > kPpwListMaxBlock) return false;   // (any block size: 8 bit multi, plain / Packed of 2 .. 8 byte symbols)
   if ((uint64_t)nBlocks * ((B + kPpwWindow - 1u) / kPpwWindow) > 0xFFFFFFF0ull) return false;            // (windows are counted in 32 bits: 16 TiB)
   return force == 1u || nBlocks >= kPpwMinBlocks;
 }
@@ -698,7 +656,7 @@ static int compress_async(int codec, const void *dIn, uint64_t U, void *dOut, ui
   // (8 bit Single / 128 bit, small containers of 1 .. 4 KiB blocks: the split encode needs regions the general workspace does not reserve --
   //  the library's own scratch has them, a caller's workspace if it was sized by hsrle_compress_workspace_size_codec)
   Workspace w = plan_workspace(U, B, false, ppw_applies(codec, (uint32_t)block_count(U, B), B));
-  if (!noSplit && split_codec_small(codec) && B <= 4096u && !pp_applies(codec, (uint32_t)w.nBlocks, B))
+  if (!noSplit && split_small(kCodecs[codec]) && B <= 4096u && !pp_applies(codec, (uint32_t)w.nBlocks, B))
   {
     // (only where the split encode will really run: its regions are 2 - 3 x the input -- ADVICE r4)
     const Workspace w2 = plan_workspace(U, B, true);
@@ -956,7 +914,7 @@ static int decompress_split_async(const void *dContainer, const hsrle_container_
                    (uint8_t *)dOut, info->uncompressedSize, info->blockSize, first, count, dStatus };
     if (g_sub[info->codec](da, kSubPacketList, (uint32_t *)dWs, st) != hipSuccess)
       return HSRLE_ERR_DEVICE;
-    return launch_expand_packets(codec_symbol_bytes((int)info->codec), da, (const uint64_t *)((const uint8_t *)dWs + countsBytes), (const uint32_t *)dWs, st) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
+    return launch_expand_packets(kCodecs[info->codec].S, da, (const uint64_t *)((const uint8_t *)dWs + countsBytes), (const uint32_t *)dWs, st) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
   }
 
   const uint32_t per = info->blockSize / SB;
@@ -1013,19 +971,6 @@ static int decompress_wave_async(const void *dContainer, const hsrle_container_i
 // ------------------------------------------------------------------------------------------------------------------
 // monolithic stream decode: index passes (hsrle_index.hip.h) + the block kernel started from entry records
 
-// symbol-state slots of the codec's decoder (IndexState<FAM>::KE): 0 plain / Single / 0-symbol Short, 1 Packed / 1-symbol list, 3, 7
-static int codec_state_slots(int c)
-{
-  static const int byVariant[8] = { 0, 1, 3, 7, 0, 1, 3, 7 };
-  if (c < 6) { static const int k8[6] = { 0, 1, 3, 7, 0, 1 }; return k8[c]; }
-  if (c < 46) return byVariant[(c - 6) & 7];
-  if (c < 50) return (c & 1) ? 1 : 0;                      // 46 sym, 47 sym_packed, 48 byte, 49 byte_packed
-  if (c < kShortBaseW) return byVariant[c - kShortBase8];
-  if (c < kGreedyBase) return byVariant[(c - kShortBaseW) & 7];
-  if (c < kSingleShort) { static const int kg[3] = { 1, 3, 7 }; return kg[(c - kGreedyBase) % 3]; }
-  return 0;
-}
-
 struct MonoPlan
 {
   uint32_t G, M, B, R, KE;
@@ -1033,7 +978,6 @@ struct MonoPlan
   uint64_t offG, offE, offOlen, offT, offEntry, offOutStart, offStateIn, offFix, offList, offMark, offCtrl, offRec, offFast, offBatch, total;
   bool range7;
 };
-
 
 // (atomics: hsrle_mono_tuning() is a TEST knob and process-global -- a call that changes it between another thread's *_workspace_size() and
 //  *_mono_dev() can make that workspace too small, which that call reports as HSRLE_ERR_CAPACITY; include/hsrle.h says so)
@@ -1058,7 +1002,7 @@ static MonoPlan plan_mono(int codec, uint32_t U, uint32_t C, uint32_t p0, uint32
   // stream), so 1 KiB in front of a region is plenty.  The other formats' junk walks live on and only find the chain by falling onto
   // one of its packet starts (1 hop in ~40 on random literals): they start with 4 KiB, and mono_decode_dev widens the look-back when
   // too many guesses turn out wrong.
-  const bool range7 = (codec == 1 || (codec >= 6 && codec < 50 && (codec == 49 || (codec < 46 && ((codec - 6) & 7) == 5))));
+  const bool range7 = hsrle::range7(kCodecs[codec]);
   // (range7 formats: regions of at most 4 KiB -- their guesses hold with a 2 KiB look-back, and the walk is one latency chain per region:
   //  the 1 GiB stream 1.47 -> 1.32 ms with 142 191 regions instead of 71 096, none guessed wrong; round 4, since the resolve pass scales)
   if (range7 && G > 4096u && !(tG >= 32u && tG <= (1u << 24))) { G = 4096u; m.G = G; }
@@ -1068,7 +1012,7 @@ static MonoPlan plan_mono(int codec, uint32_t U, uint32_t C, uint32_t p0, uint32
   m.range7 = range7;
   m.R = (uint32_t)(((uint64_t)(C - p0) + G - 1u) / G);
   if (m.R == 0u) m.R = 1u;
-  m.KE = (uint32_t)codec_state_slots(codec);
+  m.KE = (uint32_t)state_slots(kCodecs[codec]);
   m.nb = ((uint64_t)U + B - 1u) / B;
   const uint64_t ks = m.KE ? m.KE : 1u;
   uint64_t at = 0;
@@ -1134,7 +1078,7 @@ static bool mono_header(int codec, const uint8_t *h16, uint32_t inSize, uint32_t
 {
   if (codec < 0 || codec >= kCodecCount)
     return false;
-  const uint32_t hs = codec_header_size(codec);
+  const uint32_t hs = header_size(kCodecs[codec]);
   if (inSize < hs)
     return false;
   memcpy(&mh->U, h16, 4);
@@ -1147,10 +1091,11 @@ static bool mono_header(int codec, const uint8_t *h16, uint32_t inSize, uint32_t
   if (hs == 9 && h16[8] == 1)
   {
     // rle8_decompress / rle8_packed_decompress switch on the mode byte (rle8_extreme_cpu.h:702-764): Single mode -> the general kernel
-    if (codec == HSRLE_RLE8_MULTI || codec == HSRLE_RLE8_PACKED_MULTI) mh->codec = codec + 4;
+    if (codec == HSRLE_RLE8_MULTI) mh->codec = HSRLE_RLE8_SINGLE;
+    if (codec == HSRLE_RLE8_PACKED_MULTI) mh->codec = HSRLE_RLE8_PACKED_SINGLE;
     mh->single = 1; mh->singleSym = h16[9]; mh->p0 = 10;
   }
-  else if (codec == kSingleShort) { mh->singleSym = h16[8]; mh->p0 = 9; }   // rleX_Xsl_short.h:1211-1216
+  else if (kCodecs[codec].fam == SHORT_SINGLE) { mh->singleSym = h16[8]; mh->p0 = 9; }   // rleX_Xsl_short.h:1211-1216
   if (mh->U == 0 || mh->C < mh->p0 + 2u || mh->C > 0x7FFFFF00u)
     return false;
   return true;
@@ -1407,58 +1352,25 @@ __global__ void k_range_status(uint32_t *status)
 // ------------------------------------------------------------------------------------------------------------------
 // monolithic stream encode by many lanes (hsrle_mono_encode.hip.h): cut behind long runs, block kernels in MONO mode, compaction
 
-// the run length every state of the codec's encoder stores (SURVEY.md A.2 LONG / the Short family's SMINL); 0 = the codec is not cut
-// (the Greedy encoders, rle8_single_short).  *pS / *pAligned: symbol bytes and sym-alignment of the codec.
-static uint32_t mono_cut_long(int codec, int *pS = nullptr, int *pAligned = nullptr, int *pListK = nullptr)
+// the cut finders (hsrle_mono_encode.hip.h) by symbol width and alignment, one lane per piece of G bytes; the run length that makes a cut: hsrle_codecs.h cut_long().
+// onlySym (8 bit symbols; device): the Single codecs' symbol -- only its runs are cuts.  blockB != 0: the pieces are those of a container's blocks.
+static void launch_cuts(int S, int aligned, const uint32_t *onlySym, dim3 grid, hipStream_t st, const uint8_t *dIn, uint64_t U, uint32_t G, uint32_t pieces, uint32_t longc,
+                        uint64_t *cutPos, uint64_t *cutSym, uint32_t *flags, uint32_t blockB = 0)
 {
-  int S = 1, al = 0, K = 0;
-  uint32_t longc = 0;
-  static const int shortK[4] = { 0, 1, 3, 7 };
-  if (codec == kSingleShort) longc = 27u;                        // rle8_single_short: runs of THE symbol of SMINL = 11 bytes are always stored; + 16, the body counts a run from where its search found it
-  else if (codec == 4) longc = 8u;                              // 8 bit Single: runs of THE symbol with count >= LONG (rle8_extreme_cpu.h:10-11, :21-23)
-  else if (codec == 5) longc = 10u;
-  else if (codec == HSRLE_RLE8_MULTI) longc = 6u;               // rle8_extreme_cpu.h:974: count >= 6 whatever the range
-  else if (codec == HSRLE_RLE8_PACKED_MULTI) longc = 11u;       // :978 (body) and :122 (tail)
-  else if (codec == 2 || codec == 3) { longc = 11u; K = codec == 2 ? 3 : 7; }   // rle8 3 / 7 symbol LUT: rleX_Xsl.h:132 with S = 1
-  else if (codec == HSRLE_RLE8_MULTI_SHORT) longc = 13u;        // rleX_Xsl_short.h: always stored from S + 12 on (0-symbol codec)
-  else if (codec > kShortBase8 && codec < kShortBase8 + 4) { longc = 12u; K = shortK[codec - kShortBase8]; }   // ... from S + 11 on with a list
-  else if (codec >= 46 && codec < 50) { S = 16; al = codec < 48 ? 1 : 0; longc = (codec == 47) ? 26u : 27u; }   // 128 bit (rle128_extreme_cpu.h:10-11; sym-aligned Packed: the hybrid of A.5 q10)
-  else
+#define HSRLE_CUTS(SS) \
+  if (aligned) hipLaunchKernelGGL((k_mono_cutsS<SS, 1>), grid, dim3(64), 0, st, dIn, U, G, pieces, longc, cutPos, cutSym, flags, blockB); \
+  else hipLaunchKernelGGL((k_mono_cutsS<SS, 0>), grid, dim3(64), 0, st, dIn, U, G, pieces, longc, cutPos, cutSym, flags, blockB)
+  switch (S)
   {
-    static const int widths[5] = { 2, 3, 4, 6, 8 };
-    if (codec >= 6 && codec < 46)
-    {
-      const int k = (codec - 6) & 7;
-      S = widths[(codec - 6) >> 3];
-      al = k < 4 ? 1 : 0;
-      if (k == 0 || k == 4) longc = (uint32_t)S + 11u;                                  // plain: rleX_extreme_cpu.h:10-11
-      else if (k == 1) longc = (uint32_t)S + 10u;                                       // sym-aligned Packed: the hybrid of A.5 q10
-      else if (k == 5) longc = (uint32_t)S + 11u;                                       // byte-aligned Packed
-      else { longc = (uint32_t)S + 10u; K = (k & 1) ? 7 : 3; }                          // LUT: rleX_Xsl.h:132
-    }
-    else if (codec >= kShortBaseW && codec < kGreedyBase)
-    {
-      const int k = (codec - kShortBaseW) & 7;
-      S = widths[(codec - kShortBaseW) >> 3];
-      al = k < 4 ? 1 : 0;
-      if (k == 0 || k == 4) longc = (uint32_t)S + 12u;                                  // 0-symbol Short codecs
-      else { longc = (uint32_t)S + 11u; K = shortK[k & 3]; }                            // 1 / 3 / 7 symbol Short codecs
-    }
-    else if (codec >= kGreedyBase && codec < kSingleShort)
-    {
-      // Greedy encoders (rleX_Xsl_short.h:746-1000): a run of SMINL = S + 11 bytes is stored whatever the state -- but the scan may enter a
-      // periodic stretch up to ~2 S bytes late (through a prefix of a listed symbol), so a stretch is a cut from S + 11 + 3 S bytes on
-      static const int kg[3] = { 1, 3, 7 };
-      S = widths[(codec - kGreedyBase) / 3];
-      al = 0;
-      K = kg[(codec - kGreedyBase) % 3];
-      longc = 4u * (uint32_t)S + 11u;
-    }
+  case 1: hipLaunchKernelGGL(k_mono_cuts8, grid, dim3(64), 0, st, dIn, U, G, pieces, longc, cutPos, cutSym, flags, onlySym, blockB); break;
+  case 16: HSRLE_CUTS(16); break;
+  case 2: HSRLE_CUTS(2); break;
+  case 3: HSRLE_CUTS(3); break;
+  case 4: HSRLE_CUTS(4); break;
+  case 6: HSRLE_CUTS(6); break;
+  default: HSRLE_CUTS(8); break;
   }
-  if (pS) *pS = S;
-  if (pAligned) *pAligned = al;
-  if (pListK) *pListK = K;
-  return longc;
+#undef HSRLE_CUTS
 }
 
 // pieces per block (= cut finder lanes; a block has at most pieces + 1 chunks).  8 pieces were measured for the list codecs that settle their
@@ -1473,26 +1385,23 @@ static uint32_t split_pieces(uint32_t B)
 }
 
 // (round 6: the codecs with a position-parallel encoder have no run list instantiation any more -- hsrle_inst_generic.inc: pp_covers; callers run behind init_tables())
-static bool run_list_codec(int codec) { return (codec <= 3 || (codec >= 6 && codec <= 45) || (codec >= kShortBase8 && codec < kGreedyBase)) && !g_pp[codec]; }
-
-// the codecs that have a many-lane chunk encoder but no run list encoder: small containers of 1 .. 4 KiB blocks take the split encode IF the
-// caller's workspace has its regions (hsrle_compress_workspace_size_codec; the library's own scratch always has)
-static bool greedy_one_symbol_list(int codec) { return codec >= kGreedyBase && codec < kSingleShort && (codec - kGreedyBase) % 3 == 0; }
-static bool split_codec_small(int codec) { return codec == 4 || codec == 5 || codec == kSingleShort || (codec >= 46 && codec < 50) || greedy_one_symbol_list(codec); }
+// (the codecs with a run list instantiation were: all but Single, 128 bit and Greedy)
+static bool run_list_codec(int codec) { const CodecInfo &ci = kCodecs[codec]; return !is_single(ci) && ci.S != 16 && !ci.greedy && !g_pp[codec]; }
 
 static bool split_encode_applies(int codec, uint64_t nBlocks, uint32_t B)
 {
   // the codecs whose ring encoders have the chunk mode, and (round 4) 8 bit Single and 128 bit with the per-lane chunk encoders of the monolithic path
-  // rle8_multi / rle8_packed_multi / rle8_{3,7}symlut (ids 0 .. 3), the plain / Packed / LUT codecs of 2 .. 8 byte symbols (ids 6 .. 45) and their Short family (ids 50 .. 93): the run list encoders take these whole
+  // rle8_multi / rle8_packed_multi / rle8_{3,7}symlut, the plain / Packed / LUT codecs of 2 .. 8 byte symbols and their Short family: the run list encoders take these whole
   if (run_list_codec(codec) && run_list_applies(nBlocks, B, 1024u, knob_u32("HSRLE_RUNLIST", 0u))) return false;
   if (nBlocks >= kSplitEncodeBelow || B < 1024u || B > (1u << 20) || (B % (kSplitPieces * 128u)) != 0u) return false;
   // Greedy: the lists of 3 / 7 symbols decide which runs the scan stores, so a chunk's list is only known when the chunk in front of it is final --
   // measured (88 MB frame, rle32_7symlut: two full passes + three repair rounds 3.7 ms against 3.1 ms with one lane per block); a list of ONE symbol
   // behind a stored run is that run's symbol, and the first guess is right
-  if (codec >= kGreedyBase && codec < kSingleShort && !greedy_one_symbol_list(codec)) return false;
-  if ((codec == 4 || codec == 5 || codec == kSingleShort) && B > 32768u) return false;   // (the per-block symbol pick holds a block in LDS: hsrle_encode8s.hip.h)
+  const CodecInfo &ci = kCodecs[codec];
+  if (ci.greedy && !greedy_one_symbol_list(ci)) return false;
+  if (is_single(ci) && B > 32768u) return false;   // (the per-block symbol pick holds a block in LDS: hsrle_encode8s.hip.h)
   init_tables();
-  return mono_cut_long(codec) != 0u && g_menc[codec] != nullptr;
+  return g_menc[codec] != nullptr;
 }
 
 // Split encode of a container (no host synchronisation: graph capturable like the plain path): cuts inside the blocks -> chunk table (block
@@ -1502,8 +1411,9 @@ static bool split_encode_applies(int codec, uint64_t nBlocks, uint32_t B)
 // size scan over the chunks, placement, offset table + compressedLength fields.
 static int compress_split(int codec, const uint8_t *dIn, uint64_t U, uint32_t B, uint32_t nBlocks, uint8_t *ws, const Workspace &w, uint64_t *offsets, uint8_t *payload, hipStream_t st)
 {
-  int S = 1, aligned = 0, listK = 0;
-  const uint32_t longc = mono_cut_long(codec, &S, &aligned, &listK);
+  const CodecInfo &ci = kCodecs[codec];
+  const int S = ci.S, listK = list_len(ci);
+  const uint32_t longc = cut_long(ci);
   const uint32_t ppb = split_pieces(B);
   const uint32_t G = B / ppb, pieces = nBlocks * ppb, maxChunks = pieces + nBlocks;
   uint64_t *cutPos = (uint64_t *)(ws + w.spCutPos), *cutSym = (uint64_t *)(ws + w.spCutSym), *idx = (uint64_t *)(ws + w.spIdx), *starts = (uint64_t *)(ws + w.spStarts);
@@ -1516,7 +1426,7 @@ static int compress_split(int codec, const uint8_t *dIn, uint64_t U, uint32_t B,
   if (zero2_async(ctrl, 128, sizes, 4ull * (maxChunks + 1ull), st) != hipSuccess)   // (graph capturable: not hipMemsetAsync, see zero_async; 256 bytes are reserved)
     return HSRLE_ERR_DEVICE;
   const dim3 cgrid((pieces + 63u) / 64u);
-  const bool single = codec == 4 || codec == 5 || codec == kSingleShort;
+  const bool single = is_single(ci);
   uint32_t *const pickTable = (uint32_t *)(ws + w.spPick);             // (8 bit Single: a byte per block)
   if (single)
   {
@@ -1528,29 +1438,16 @@ static int compress_split(int codec, const uint8_t *dIn, uint64_t U, uint32_t B,
     if (g_menc[codec](pa, pm, st) != hipSuccess)
       return HSRLE_ERR_DEVICE;
   }
-#define HSRLE_CUTS(SS) \
-  if (aligned) hipLaunchKernelGGL((k_mono_cutsS<SS, 1>), cgrid, dim3(64), 0, st, dIn, U, G, pieces, longc, cutPos, cutSym, flags, B); \
-  else hipLaunchKernelGGL((k_mono_cutsS<SS, 0>), cgrid, dim3(64), 0, st, dIn, U, G, pieces, longc, cutPos, cutSym, flags, B)
-  switch (S)
-  {
-  case 1: if (!single) hipLaunchKernelGGL(k_mono_cuts8, cgrid, dim3(64), 0, st, dIn, U, G, pieces, longc, cutPos, cutSym, flags, (const uint32_t *)nullptr, B); break;
-  case 16: HSRLE_CUTS(16); break;
-  case 2: HSRLE_CUTS(2); break;
-  case 3: HSRLE_CUTS(3); break;
-  case 4: HSRLE_CUTS(4); break;
-  case 6: HSRLE_CUTS(6); break;
-  default: HSRLE_CUTS(8); break;
-  }
-#undef HSRLE_CUTS
+  if (!single) launch_cuts(S, ci.aligned, nullptr, cgrid, st, dIn, U, G, pieces, longc, cutPos, cutSym, flags, B);   // (Single: the pick above left the cuts)
   if (scan_sizes(flags, pieces, idx, ws, sw, st) != hipSuccess)
     return HSRLE_ERR_DEVICE;
   if (listK != 0)
     hipLaunchKernelGGL(k_mono_list_default, dim3((maxChunks + 255u) / 256u), dim3(256), 0, st, maxChunks, (uint32_t)listK, (uint32_t)S, guess);
   // list codecs of 2 .. 8 byte symbols settle their lists INSIDE the encode kernel: a wave takes the chunks of kSplitGroup whole blocks (k_encodeS_blocks)
   const uint32_t kSplitGroup = 64u / (ppb + 1u);                         // blocks per wave: x (ppb + 1) chunks at most <= a wave's 64 lanes
-  const bool inKernelLists = listK != 0 && S > 1 && codec < kGreedyBase;   // (Greedy: one lane per chunk, lists between launches like the 8 bit codecs)
+  const bool inKernelLists = listK != 0 && S > 1 && !ci.greedy;   // (Greedy: one lane per chunk, lists between launches like the 8 bit codecs)
   hipLaunchKernelGGL(k_split_scatter, dim3((pieces + 255u) / 256u), dim3(256), 0, st, (const uint64_t *)cutPos, (const uint64_t *)cutSym, (const uint32_t *)flags, (const uint64_t *)idx, pieces,
-                     ppb, nBlocks, U, B, starts, listK ? guess : syms, slotOff, firstChunk, ctrl, (uint32_t)listK | ((codec >= kGreedyBase && listK == 1) ? kSplitGuessCutSym : 0u), inKernelLists ? kSplitGroup : 0u);
+                     ppb, nBlocks, U, B, starts, listK ? guess : syms, slotOff, firstChunk, ctrl, (uint32_t)listK | (greedy_one_symbol_list(ci) ? kSplitGuessCutSym : 0u), inKernelLists ? kSplitGroup : 0u);
 
   EncodeArgs ea{ dIn, U, B, inKernelLists ? ((nBlocks + kSplitGroup - 1u) / kSplitGroup) * 64u : maxChunks, ws + w.spSlots, 0u, sizes };
   ea.ringSel = ctrl;                                                     // chunk mode with B: ctrl[0] = the number of chunks, [1] = blocks per wave (0: chunks in a row), [2] = blocks
@@ -1582,7 +1479,7 @@ static int compress_split(int codec, const uint8_t *dIn, uint64_t U, uint32_t B,
         return HSRLE_ERR_DEVICE;
     }
   }
-  const bool laneChunks = single || S == 16 || codec >= kGreedyBase;     // per-lane chunk encoders: a chunk that missed its boundary run says so with size 0
+  const bool laneChunks = single || S == 16 || ci.greedy;           // per-lane chunk encoders: a chunk that missed its boundary run says so with size 0
   if (laneChunks)
     hipLaunchKernelGGL(k_split_check, dim3((nBlocks + 255u) / 256u), dim3(256), 0, st, (const uint32_t *)firstChunk, (const uint64_t *)starts, (const uint32_t *)sizes, nBlocks, ctrl + 24);   // (ctrl[24]: zeroed above; outside the rounds' counters ctrl[9 ..] and the Single encoders' ctrl[12] -- ADVICE r5)
   if (scan_sizes(sizes, maxChunks, chunkOff, ws, sw, st) != hipSuccess)
@@ -1606,23 +1503,16 @@ static thread_local uint32_t g_monoEncLast[4] = { 0, 0, 0, 0 };   // this thread
 struct MonoEncPlan
 {
   uint32_t G, pieces;
-  bool windowed;                                       // mono_chunk_mode_codec(): chunks of any length by the windowed position-parallel encoders (hsrle_encode8pw.hip.h, hsrle_encodeSpw.hip.h)
+  bool windowed;                                       // hsrle_codecs.h chunk_mode(): chunks of any length by the windowed position-parallel encoders (hsrle_encode8pw.hip.h, hsrle_encodeSpw.hip.h)
   uint64_t offCutPos, offCutSym, offFlags, offIdx, offStarts, offSyms, offSlotOff, offSizes, offOffsets, offL1, offL2, offL3, offCtrl, offSlots, total;
   uint64_t offGuess, offListOut, offRoll1, offRoll2;   // codecs with a move-to-front list: 8 words per chunk / per 64 / per 4096 chunks
   uint64_t offPick;                                    // 8 bit Single: the symbol pick's sums (k_single_pick_mono)
   uint64_t offJobs; uint32_t jobCap;                   // 8 bit Single: literal stretches noted by the chunk encoders for k_copy_jobs
 };
 
-// the codecs whose encoder state at a cut is fixed by the cut itself (no list, or a one-symbol list = the cut's symbol): rle8_multi / rle8_packed_multi, the plain /
-// Packed codecs of 2 .. 8 byte symbols (ids 6 + 8 w + {0, 1, 4, 5}), the Short codecs with no list or a one-symbol list (54 + 8 w + {0, 1, 4, 5}, 50, 51)
-static bool mono_chunk_mode_codec(int codec)
-{
-  if (codec == HSRLE_RLE8_MULTI || codec == HSRLE_RLE8_PACKED_MULTI || codec == kShortBase8 || codec == kShortBase8 + 1) return true;
-  const int v = (codec >= 6 && codec < 46) ? (codec - 6) & 7 : ((codec >= kShortBaseW && codec < kGreedyBase) ? (codec - kShortBaseW) & 7 : -1);
-  return v == 0 || v == 1 || v == 4 || v == 5;
-}
-static PpwLaunch mono_ppw_launcher(int codec) { return !mono_chunk_mode_codec(codec) ? nullptr : (codec <= 1 ? g_ppw[codec] : g_ppwSM[codec]); }
-static uint32_t mono_ppw_state_words(int codec) { return codec <= 1 ? kPpwStateWords : kPpwSStateWords; }
+// the codecs whose encoder state at a cut is fixed by the cut itself (hsrle_codecs.h: chunk_mode): the 8 bit pair's windowed encoder, or the chunk mode of hsrle_encodeSpw.hip.h
+static PpwLaunch mono_ppw_launcher(int codec) { return !chunk_mode(kCodecs[codec]) ? nullptr : (g_ppw[codec] ? g_ppw[codec] : g_ppwSM[codec]); }
+static uint32_t mono_ppw_state_words(int codec) { return g_ppw[codec] ? kPpwStateWords : kPpwSStateWords; }
 static bool mono_windowed(int codec) { return mono_ppw_launcher(codec) != nullptr && kPpwMinBlocks != 0xFFFFFFFFu && knob_u32("HSRLE_PP", 0u) != 2u; }
 
 static MonoEncPlan plan_mono_encode(uint32_t U, int codec, bool lists = true)
@@ -1693,12 +1583,13 @@ static int mono_encode_dev(int codec, const uint8_t *dIn, uint32_t U, uint8_t *d
                            uint32_t *dStatus = nullptr)
 {
   init_tables();
-  int S = 1, aligned = 0, listK = 0;
-  const uint32_t longc = mono_cut_long(codec, &S, &aligned, &listK);
-  if (!g_menc[codec] || longc == 0u)
+  const CodecInfo &ci = kCodecs[codec];
+  const int S = ci.S, listK = list_len(ci);
+  const uint32_t longc = cut_long(ci);
+  if (!g_menc[codec])
     return HSRLE_ERR_UNSUPPORTED;
-  const bool single = codec == 4 || codec == 5 || codec == kSingleShort;
-  const uint32_t hs = codec_header_size(codec) + (single ? 1u : 0u);   // (Single: the symbol byte follows the header)
+  const bool single = is_single(ci);
+  const uint32_t hs = header_size(ci) + (single ? 1u : 0u);   // (Single: the symbol byte follows the header)
   uint64_t *cutPos = (uint64_t *)(ws + m.offCutPos), *idx = (uint64_t *)(ws + m.offIdx), *starts = (uint64_t *)(ws + m.offStarts), *slotOff = (uint64_t *)(ws + m.offSlotOff);
   uint64_t *offsets = (uint64_t *)(ws + m.offOffsets);
   uint64_t *cutSym = (uint64_t *)(ws + m.offCutSym), *syms = (uint64_t *)(ws + m.offSyms);
@@ -1719,20 +1610,7 @@ static int mono_encode_dev(int codec, const uint8_t *dIn, uint32_t U, uint8_t *d
     hipLaunchKernelGGL(k_single_pick_final, dim3(1), dim3(64), 0, st, dIn, U, table, ctrl + 8);
   }
   const dim3 cgrid((m.pieces + 63u) / 64u);
-#define HSRLE_CUTS(SS) \
-  if (aligned) hipLaunchKernelGGL((k_mono_cutsS<SS, 1>), cgrid, dim3(64), 0, st, dIn, (uint64_t)U, m.G, m.pieces, longc, cutPos, cutSym, flags); \
-  else hipLaunchKernelGGL((k_mono_cutsS<SS, 0>), cgrid, dim3(64), 0, st, dIn, (uint64_t)U, m.G, m.pieces, longc, cutPos, cutSym, flags)
-  switch (S)
-  {
-  case 1: hipLaunchKernelGGL(k_mono_cuts8, cgrid, dim3(64), 0, st, dIn, (uint64_t)U, m.G, m.pieces, longc, cutPos, cutSym, flags, single ? (const uint32_t *)(ctrl + 8) : (const uint32_t *)nullptr); break;
-  case 2: HSRLE_CUTS(2); break;
-  case 3: HSRLE_CUTS(3); break;
-  case 4: HSRLE_CUTS(4); break;
-  case 6: HSRLE_CUTS(6); break;
-  case 16: HSRLE_CUTS(16); break;
-  default: HSRLE_CUTS(8); break;
-  }
-#undef HSRLE_CUTS
+  launch_cuts(S, ci.aligned, single ? (const uint32_t *)(ctrl + 8) : (const uint32_t *)nullptr, cgrid, st, dIn, (uint64_t)U, m.G, m.pieces, longc, cutPos, cutSym, flags);
   if (scan_sizes(flags, m.pieces, idx, ws, w, st) != hipSuccess)
     return HSRLE_ERR_DEVICE;
   hipLaunchKernelGGL(k_mono_scatter, dim3((m.pieces + 255u) / 256u), dim3(256), 0, st, (const uint64_t *)cutPos, (const uint64_t *)cutSym, (const uint32_t *)flags, (const uint64_t *)idx,
@@ -1852,9 +1730,9 @@ static int mono_encode_dev(int codec, const uint8_t *dIn, uint32_t U, uint8_t *d
   if (scan_sizes(sizes, chunks, offsets, ws, w, st) != hipSuccess)
     return HSRLE_ERR_DEVICE;
   launch_compact_var(false, (const uint8_t *)(ws + m.offSlots), (const uint64_t *)slotOff, (const uint64_t *)offsets, dOut + hs, chunks, st);
-  if (single || codec >= kGreedyBase)
+  if (single || ci.greedy)
     hipLaunchKernelGGL(k_mono_zero_sizes, dim3((chunks + 255u) / 256u), dim3(256), 0, st, (const uint32_t *)sizes, chunks, ctrl + 5);
-  hipLaunchKernelGGL(k_mono_finish, dim3(1), dim3(64), 0, st, dOut, U, hs, (const uint64_t *)offsets, (const uint32_t *)ctrl, ctrl, codec == kSingleShort ? 1u : 0u);
+  hipLaunchKernelGGL(k_mono_finish, dim3(1), dim3(64), 0, st, dOut, U, hs, (const uint64_t *)offsets, (const uint32_t *)ctrl, ctrl, ci.fam == SHORT_SINGLE ? 1u : 0u);
   uint32_t tail[4] = { 0, 0, 0, 0 };
   if (hipGetLastError() != hipSuccess || hipMemcpyAsync(tail, ctrl + 2, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
     return HSRLE_ERR_DEVICE;
@@ -1890,7 +1768,7 @@ static uint32_t mono_compress(int codec, const uint8_t *pIn, uint32_t inSize, ui
     return 0;
 
   // many lanes where the codec allows it (cuts behind long runs, hsrle_mono_encode.hip.h); else -- and for inputs of one piece -- one lane
-  if (mono_cut_long(codec) != 0u && g_menc[codec])
+  if (g_menc[codec])
   {
     const MonoEncPlan m = plan_mono_encode(inSize, codec);
     if (m.pieces >= 2u)
@@ -1934,7 +1812,7 @@ static uint32_t mono_decompress(int codec, const uint8_t *pIn, uint32_t inSize, 
   // argument + header checks of the reference (rle8_extreme_cpu.h:704-712, rleX_extreme_cpu.h:84-91, rleX_Xsl.h:1850-1858)
   if (pIn == nullptr || pOut == nullptr || inSize == 0 || outSize == 0)
     return 0;
-  if (codec < 0 || codec >= kCodecCount || inSize < codec_header_size(codec))
+  if (codec < 0 || codec >= kCodecCount || inSize < header_size(kCodecs[codec]))
     return 0;
   uint8_t h16[16] = { 0 };
   memcpy(h16, pIn, inSize < 16u ? inSize : 16u);
@@ -2145,11 +2023,11 @@ int hsrle_codec_from_name(const char *name)
 {
   if (!name) return -1;
   for (int k = 0; k < kCodecCount; k++)
-    if (strcmp(name, kCodecNames[k]) == 0) return k;
+    if (strcmp(name, kCodecs[k].name) == 0) return k;
   return -1;
 }
 
-const char *hsrle_codec_name(int codec) { return (codec >= 0 && codec < kCodecCount) ? kCodecNames[codec] : nullptr; }
+const char *hsrle_codec_name(int codec) { return (codec >= 0 && codec < kCodecCount) ? kCodecs[codec].name : nullptr; }
 
 const char *hsrle_status_string(int s)
 {
@@ -2669,10 +2547,11 @@ uint32_t hsrle_decompress_mono(int codec, const uint8_t *pIn, uint32_t inSize, u
 #define HSRLE_DEF_PAIR(name, id)                                                                                                                             \
   uint32_t name##_compress(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize) { return mono_compress(id, pIn, inSize, pOut, outSize); } \
   uint32_t name##_decompress(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize) { return mono_decompress(id, pIn, inSize, pOut, outSize); }
-#define HSRLE_DEF_WIDTH(W, base)                                                                                               \
-  HSRLE_DEF_PAIR(rle##W##_sym, base + 0) HSRLE_DEF_PAIR(rle##W##_sym_packed, base + 1) HSRLE_DEF_PAIR(rle##W##_3symlut_sym, base + 2) \
-  HSRLE_DEF_PAIR(rle##W##_7symlut_sym, base + 3) HSRLE_DEF_PAIR(rle##W##_byte, base + 4) HSRLE_DEF_PAIR(rle##W##_byte_packed, base + 5) \
-  HSRLE_DEF_PAIR(rle##W##_3symlut_byte, base + 6) HSRLE_DEF_PAIR(rle##W##_7symlut_byte, base + 7)
+#define HSRLE_DEF_WIDTH(W)                                                                                                                                  \
+  HSRLE_DEF_PAIR(rle##W##_sym, codec_id(PLAIN, W / 8, 1)) HSRLE_DEF_PAIR(rle##W##_sym_packed, codec_id(PACKED, W / 8, 1))                                     \
+  HSRLE_DEF_PAIR(rle##W##_3symlut_sym, codec_id(LUT3, W / 8, 1)) HSRLE_DEF_PAIR(rle##W##_7symlut_sym, codec_id(LUT7, W / 8, 1))                               \
+  HSRLE_DEF_PAIR(rle##W##_byte, codec_id(PLAIN, W / 8, 0)) HSRLE_DEF_PAIR(rle##W##_byte_packed, codec_id(PACKED, W / 8, 0))                                   \
+  HSRLE_DEF_PAIR(rle##W##_3symlut_byte, codec_id(LUT3, W / 8, 0)) HSRLE_DEF_PAIR(rle##W##_7symlut_byte, codec_id(LUT7, W / 8, 0))
 
 uint32_t rle8_multi_compress(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize) { return mono_compress(HSRLE_RLE8_MULTI, pIn, inSize, pOut, outSize); }
 uint32_t rle8_single_compress(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize) { return mono_compress(HSRLE_RLE8_SINGLE, pIn, inSize, pOut, outSize); }
@@ -2682,39 +2561,40 @@ uint32_t rle8_packed_single_compress(const uint8_t *pIn, const uint32_t inSize, 
 uint32_t rle8_packed_decompress(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize) { return mono_decompress(HSRLE_RLE8_PACKED_MULTI, pIn, inSize, pOut, outSize); }
 HSRLE_DEF_PAIR(rle8_3symlut, HSRLE_RLE8_3SYMLUT)
 HSRLE_DEF_PAIR(rle8_7symlut, HSRLE_RLE8_7SYMLUT)
-HSRLE_DEF_WIDTH(16, 6)
-HSRLE_DEF_WIDTH(24, 14)
-HSRLE_DEF_WIDTH(32, 22)
-HSRLE_DEF_WIDTH(48, 30)
-HSRLE_DEF_WIDTH(64, 38)
+HSRLE_DEF_WIDTH(16)
+HSRLE_DEF_WIDTH(24)
+HSRLE_DEF_WIDTH(32)
+HSRLE_DEF_WIDTH(48)
+HSRLE_DEF_WIDTH(64)
 HSRLE_DEF_PAIR(rle128_sym, HSRLE_RLE128_SYM)
 HSRLE_DEF_PAIR(rle128_sym_packed, HSRLE_RLE128_SYM_PACKED)
 HSRLE_DEF_PAIR(rle128_byte, HSRLE_RLE128_BYTE)
 HSRLE_DEF_PAIR(rle128_byte_packed, HSRLE_RLE128_BYTE_PACKED)
 // Short family
-#define HSRLE_DEF_SHORT_WIDTH(W, base)                                                                                                   \
-  HSRLE_DEF_PAIR(rle##W##_sym_short, base + 0) HSRLE_DEF_PAIR(rle##W##_1symlut_sym_short, base + 1) HSRLE_DEF_PAIR(rle##W##_3symlut_sym_short, base + 2) \
-  HSRLE_DEF_PAIR(rle##W##_7symlut_sym_short, base + 3) HSRLE_DEF_PAIR(rle##W##_byte_short, base + 4) HSRLE_DEF_PAIR(rle##W##_1symlut_byte_short, base + 5) \
-  HSRLE_DEF_PAIR(rle##W##_3symlut_byte_short, base + 6) HSRLE_DEF_PAIR(rle##W##_7symlut_byte_short, base + 7)
+#define HSRLE_DEF_SHORT_WIDTH(W)                                                                                                                            \
+  HSRLE_DEF_PAIR(rle##W##_sym_short, codec_id(SHORT0, W / 8, 1)) HSRLE_DEF_PAIR(rle##W##_1symlut_sym_short, codec_id(SHORT1, W / 8, 1))                       \
+  HSRLE_DEF_PAIR(rle##W##_3symlut_sym_short, codec_id(SHORT3, W / 8, 1)) HSRLE_DEF_PAIR(rle##W##_7symlut_sym_short, codec_id(SHORT7, W / 8, 1))               \
+  HSRLE_DEF_PAIR(rle##W##_byte_short, codec_id(SHORT0, W / 8, 0)) HSRLE_DEF_PAIR(rle##W##_1symlut_byte_short, codec_id(SHORT1, W / 8, 0))                     \
+  HSRLE_DEF_PAIR(rle##W##_3symlut_byte_short, codec_id(SHORT3, W / 8, 0)) HSRLE_DEF_PAIR(rle##W##_7symlut_byte_short, codec_id(SHORT7, W / 8, 0))
 HSRLE_DEF_PAIR(rle8_multi_short, HSRLE_RLE8_MULTI_SHORT)
 HSRLE_DEF_PAIR(rle8_1symlut_short, HSRLE_RLE8_1SYMLUT_SHORT)
 HSRLE_DEF_PAIR(rle8_3symlut_short, HSRLE_RLE8_3SYMLUT_SHORT)
 HSRLE_DEF_PAIR(rle8_7symlut_short, HSRLE_RLE8_7SYMLUT_SHORT)
-HSRLE_DEF_SHORT_WIDTH(16, 54)
-HSRLE_DEF_SHORT_WIDTH(24, 62)
-HSRLE_DEF_SHORT_WIDTH(32, 70)
-HSRLE_DEF_SHORT_WIDTH(48, 78)
-HSRLE_DEF_SHORT_WIDTH(64, 86)
+HSRLE_DEF_SHORT_WIDTH(16)
+HSRLE_DEF_SHORT_WIDTH(24)
+HSRLE_DEF_SHORT_WIDTH(32)
+HSRLE_DEF_SHORT_WIDTH(48)
+HSRLE_DEF_SHORT_WIDTH(64)
 // Greedy encoders: only a compress entry point each (src/rle.h:398-416); their streams go to rle{W}_{K}symlut_byte_short_decompress
-#define HSRLE_DEF_GREEDY(W, base)                                                                                                                                     \
-  uint32_t rle##W##_1symlut_byte_short_compress_greedy(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize) { return mono_compress(base + 0, pIn, inSize, pOut, outSize); } \
-  uint32_t rle##W##_3symlut_byte_short_compress_greedy(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize) { return mono_compress(base + 1, pIn, inSize, pOut, outSize); } \
-  uint32_t rle##W##_7symlut_byte_short_compress_greedy(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize) { return mono_compress(base + 2, pIn, inSize, pOut, outSize); }
-HSRLE_DEF_GREEDY(16, 94)
-HSRLE_DEF_GREEDY(24, 97)
-HSRLE_DEF_GREEDY(32, 100)
-HSRLE_DEF_GREEDY(48, 103)
-HSRLE_DEF_GREEDY(64, 106)
+#define HSRLE_DEF_GREEDY(W)                                                                                                                                           \
+  uint32_t rle##W##_1symlut_byte_short_compress_greedy(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize) { return mono_compress(codec_id(SHORT1, W / 8, 0, true), pIn, inSize, pOut, outSize); } \
+  uint32_t rle##W##_3symlut_byte_short_compress_greedy(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize) { return mono_compress(codec_id(SHORT3, W / 8, 0, true), pIn, inSize, pOut, outSize); } \
+  uint32_t rle##W##_7symlut_byte_short_compress_greedy(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize) { return mono_compress(codec_id(SHORT7, W / 8, 0, true), pIn, inSize, pOut, outSize); }
+HSRLE_DEF_GREEDY(16)
+HSRLE_DEF_GREEDY(24)
+HSRLE_DEF_GREEDY(32)
+HSRLE_DEF_GREEDY(48)
+HSRLE_DEF_GREEDY(64)
 HSRLE_DEF_PAIR(rle8_single_short, HSRLE_RLE8_SINGLE_SHORT)
 
 // ---- container API ----
@@ -2740,7 +2620,7 @@ uint64_t hsrle_compress_workspace_size_codec(int codec, uint64_t inSize, uint32_
   if (!valid_block_size(blockSize) || inSize == 0 || codec < 0 || codec >= kCodecCount) return 0;
   init_tables();
   // (round 6: 8 bit Single and 128 bit containers of <= 4 KiB blocks are position-parallel -- no split regions; rle8_single_short and the Greedy codecs with a one-symbol list still take them)
-  const bool split = split_codec_small(codec) && blockSize <= 4096u && !pp_applies(codec, (uint32_t)block_count(inSize, blockSize), blockSize);
+  const bool split = split_small(kCodecs[codec]) && blockSize <= 4096u && !pp_applies(codec, (uint32_t)block_count(inSize, blockSize), blockSize);
   // (... and the windowed encoders take blocks above 4 KiB without the split regions: 1.05 x the input instead of 3.4 x)
   return plan_workspace(inSize, blockSize, split, block_count(inSize, blockSize) <= 0xFFFFFFF0ull && ppw_applies(codec, (uint32_t)block_count(inSize, blockSize), blockSize)).total;
 }
@@ -2930,7 +2810,7 @@ void hsrle_mono_encode_stats(uint32_t stats[4])
 
 uint64_t hsrle_compress_mono_workspace_size(int codec, uint32_t inSize)
 {
-  if (codec < 0 || codec >= kCodecCount || inSize == 0 || inSize > (1u << 30) || mono_cut_long(codec) == 0u) return 0;
+  if (codec < 0 || codec >= kCodecCount || inSize == 0 || inSize > (1u << 30)) return 0;
   return plan_mono_encode(inSize, codec).total;
 }
 
@@ -2938,7 +2818,7 @@ int hsrle_compress_mono_dev(int codec, const void *dIn, uint32_t inSize, void *d
                             uint32_t *pChunks, void *stream)
 {
   if (!dIn || !dOut || !dWorkspace || !pStreamSize || codec < 0 || codec >= kCodecCount || inSize == 0) return HSRLE_ERR_ARGUMENT;
-  if (inSize > (1u << 30) || mono_cut_long(codec) == 0u) return HSRLE_ERR_UNSUPPORTED;
+  if (inSize > (1u << 30)) return HSRLE_ERR_UNSUPPORTED;
   if (outCapacity < bounds32(inSize)) return HSRLE_ERR_CAPACITY;
   if (!device_ok()) return HSRLE_ERR_DEVICE;
   const MonoEncPlan m = plan_mono_encode(inSize, codec);
@@ -2950,11 +2830,11 @@ int hsrle_compress_mono_dev_async(int codec, const void *dIn, uint32_t inSize, v
                                   void *stream)
 {
   if (!dIn || !dOut || !dWorkspace || codec < 0 || codec >= kCodecCount || inSize == 0) return HSRLE_ERR_ARGUMENT;
-  if (inSize > (1u << 30) || mono_cut_long(codec) == 0u) return HSRLE_ERR_UNSUPPORTED;
+  if (inSize > (1u << 30)) return HSRLE_ERR_UNSUPPORTED;
   if (outCapacity < bounds32(inSize)) return HSRLE_ERR_CAPACITY;
   if (!device_ok()) return HSRLE_ERR_DEVICE;
   const MonoEncPlan m = plan_mono_encode(inSize, codec);
-  if (codec > 1 || !m.windowed) return HSRLE_ERR_UNSUPPORTED;             // (the 8 bit pair only, as ever: the other codecs take hsrle_compress_mono_dev_enqueue)
+  if (!g_ppw[codec] || !m.windowed) return HSRLE_ERR_UNSUPPORTED;         // (the 8 bit pair only, as ever: the other codecs take hsrle_compress_mono_dev_enqueue)
   if (workspaceSize < m.total) return HSRLE_ERR_CAPACITY;
   return mono_encode_dev(codec, (const uint8_t *)dIn, inSize, (uint8_t *)dOut, (uint8_t *)dWorkspace, m, nullptr, dStreamSize, (hipStream_t)stream);
 }
@@ -2963,7 +2843,7 @@ int hsrle_compress_mono_dev_enqueue(int codec, const void *dIn, uint32_t inSize,
                                     uint32_t *dStreamSize, uint32_t *dStatus, void *stream)
 {
   if (codec < 0 || codec >= kCodecCount) return HSRLE_ERR_ARGUMENT;
-  if (!mono_chunk_mode_codec(codec)) return HSRLE_ERR_UNSUPPORTED;        // (before the device: the codec set is a property of the library)
+  if (!chunk_mode(kCodecs[codec])) return HSRLE_ERR_UNSUPPORTED;         // (before the device: the codec set is a property of the library)
   if (!dIn || !dOut || !dWorkspace || !dStatus || inSize == 0) return HSRLE_ERR_ARGUMENT;
   if (inSize > (1u << 30)) return HSRLE_ERR_UNSUPPORTED;
   if (outCapacity < bounds32(inSize)) return HSRLE_ERR_CAPACITY;
@@ -2977,7 +2857,7 @@ int hsrle_compress_mono_dev_enqueue(int codec, const void *dIn, uint32_t inSize,
 uint64_t hsrle_decompress_mono_workspace_size(int codec, uint32_t uncompressedSize, uint32_t compressedSize)
 {
   if (codec < 0 || codec >= kCodecCount || uncompressedSize == 0 || compressedSize < 10u) return 0;
-  return plan_mono(codec, uncompressedSize, compressedSize, codec_header_size(codec)).total + 16u;   // (+ 16: a workspace that is not 16-byte aligned is aligned here)
+  return plan_mono(codec, uncompressedSize, compressedSize, header_size(kCodecs[codec])).total + 16u;   // (+ 16: a workspace that is not 16-byte aligned is aligned here)
 }
 
 // the workspace is cleared with 16-byte stores (mono_prepare): a caller that sub-allocates from a byte pool may hand over any address -- it is rounded up, what
@@ -2992,7 +2872,7 @@ static inline void mono_align_workspace(void *&dWorkspace, uint64_t &workspaceSi
 int hsrle_decompress_mono_dev(int codec, const void *dStream, uint32_t streamSize, void *dOut, uint64_t outCapacity, void *dWorkspace, uint64_t workspaceSize,
                               uint32_t *pUncompressedSize, uint32_t *pStats, void *stream)
 {
-  if (!dStream || !dOut || !dWorkspace || codec < 0 || codec >= kCodecCount || streamSize < codec_header_size(codec) || ((uintptr_t)dStream & 127u) != 0u)
+  if (!dStream || !dOut || !dWorkspace || codec < 0 || codec >= kCodecCount || streamSize < header_size(kCodecs[codec]) || ((uintptr_t)dStream & 127u) != 0u)
     return HSRLE_ERR_ARGUMENT;
   mono_align_workspace(dWorkspace, workspaceSize);
   if (!device_ok()) return HSRLE_ERR_DEVICE;
@@ -3013,7 +2893,7 @@ int hsrle_decompress_mono_dev_async(int codec, const void *dStream, const uint8_
                                     uint64_t workspaceSize, uint32_t *pUncompressedSize, uint32_t *dStatus, void *stream)
 {
   // (the same smallest stream as the synchronous entry: the codec's header; pHeader16 holds the stream's first min(16, streamSize) bytes, zeros behind them)
-  if (!dStream || !pHeader16 || !dOut || !dWorkspace || !dStatus || codec < 0 || codec >= kCodecCount || streamSize < codec_header_size(codec) || ((uintptr_t)dStream & 127u) != 0u)
+  if (!dStream || !pHeader16 || !dOut || !dWorkspace || !dStatus || codec < 0 || codec >= kCodecCount || streamSize < header_size(kCodecs[codec]) || ((uintptr_t)dStream & 127u) != 0u)
     return HSRLE_ERR_ARGUMENT;
   mono_align_workspace(dWorkspace, workspaceSize);
   if (!device_ok()) return HSRLE_ERR_DEVICE;
@@ -3035,20 +2915,20 @@ int hsrle_decompress_mono_dev_async(int codec, const void *dStream, const uint8_
 uint64_t hsrle_mono_index_size(int codec, uint32_t uncompressedSize, uint32_t compressedSize, uint32_t spacing)
 {
   if (codec < 0 || codec >= kCodecCount || uncompressedSize == 0 || compressedSize < 10u || (spacing != 0u && !valid_spacing(spacing))) return 0;
-  const MonoPlan m = plan_mono(codec, uncompressedSize, compressedSize, codec_header_size(codec), spacing);
+  const MonoPlan m = plan_mono(codec, uncompressedSize, compressedSize, header_size(kCodecs[codec]), spacing);
   return kMonoIndexHeaderBytes + m.nb * kMonoIndexRecordBytes;
 }
 
 uint64_t hsrle_mono_index_workspace_size(int codec, uint32_t uncompressedSize, uint32_t compressedSize, uint32_t spacing)
 {
   if (codec < 0 || codec >= kCodecCount || uncompressedSize == 0 || compressedSize < 10u || (spacing != 0u && !valid_spacing(spacing))) return 0;
-  return plan_mono(codec, uncompressedSize, compressedSize, codec_header_size(codec), spacing).total + 16u;   // (+ 16: as hsrle_decompress_mono_workspace_size)
+  return plan_mono(codec, uncompressedSize, compressedSize, header_size(kCodecs[codec]), spacing).total + 16u;   // (+ 16: as hsrle_decompress_mono_workspace_size)
 }
 
 int hsrle_mono_index_build_dev(int codec, const void *dStream, uint32_t streamSize, uint32_t spacing, void *dIndex, uint64_t indexCapacity, void *dWorkspace,
                                uint64_t workspaceSize, hsrle_mono_index_info_t *pInfo, void *stream)
 {
-  if (!dStream || !dIndex || !dWorkspace || codec < 0 || codec >= kCodecCount || streamSize < codec_header_size(codec) || ((uintptr_t)dStream & 127u) != 0u ||
+  if (!dStream || !dIndex || !dWorkspace || codec < 0 || codec >= kCodecCount || streamSize < header_size(kCodecs[codec]) || ((uintptr_t)dStream & 127u) != 0u ||
       ((uintptr_t)dIndex & 15u) != 0u || (spacing != 0u && !valid_spacing(spacing)))
     return HSRLE_ERR_ARGUMENT;
   mono_align_workspace(dWorkspace, workspaceSize);

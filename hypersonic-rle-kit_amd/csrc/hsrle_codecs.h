@@ -1,0 +1,132 @@
+// hsrle_codecs.h -- what every codec IS, said once: one row per codec id (include/hsrle.h: hsrle_codec_t), and the facts the host code derives from a row.
+// Host-only and free of HIP: a plain C++17 compiler can include it (tests/test_codec_traits.py does).  The kernels are instantiated as <FAM, S, AL>
+// (hsrle_common.hip.h: Traits); codec_id() is the way from those template arguments to the slot of a launch table.
+#pragma once
+#include "../../include/hsrle.h"
+
+#include <stdint.h>
+
+namespace hsrle {
+
+enum Family : int { PLAIN = 0, PACKED = 1, LUT3 = 2, LUT7 = 3, SINGLE = 4, PACKED_SINGLE = 5,
+                    SHORT0 = 6, SHORT1 = 7, SHORT3 = 8, SHORT7 = 9,     // Short family: 0 / 1 / 3 / 7 symbol LUT, one-byte packed headers
+                    SHORT_SINGLE = 10 };                                // rle8_single_short: one symbol per stream, none in the packets
+
+struct CodecInfo
+{
+  const char *name;   // names follow the reference: src/rle.h, src/codec_funcs.h:270-410
+  Family fam;
+  uint8_t S;          // symbol bytes
+  uint8_t aligned;    // sym-aligned (1) or byte-aligned (0); 0 for 8 bit symbols
+  bool greedy;        // a Greedy ENCODER of the family's grammar
+};
+
+constexpr int kCodecCount = 110;                 // 50 extreme codecs + 44 of the Short family + 15 Greedy encoders (8f-1) + rle8_single_short
+constexpr CodecInfo kCodecs[kCodecCount] = {
+  // 8 bit symbols (reference: src/rle.h:101-103, :173-175, :199-208)
+  { "rle8_multi", PLAIN, 1, 0, false }, { "rle8_packed_multi", PACKED, 1, 0, false }, { "rle8_3symlut", LUT3, 1, 0, false },
+  { "rle8_7symlut", LUT7, 1, 0, false }, { "rle8_single", SINGLE, 1, 0, false }, { "rle8_packed_single", PACKED_SINGLE, 1, 0, false },
+  // 2 .. 8 byte symbols, per width: sym-aligned plain / Packed / 3 / 7 symbol LUT, then the byte-aligned four
+  { "rle16_sym", PLAIN, 2, 1, false }, { "rle16_sym_packed", PACKED, 2, 1, false }, { "rle16_3symlut_sym", LUT3, 2, 1, false }, { "rle16_7symlut_sym", LUT7, 2, 1, false },
+  { "rle16_byte", PLAIN, 2, 0, false }, { "rle16_byte_packed", PACKED, 2, 0, false }, { "rle16_3symlut_byte", LUT3, 2, 0, false }, { "rle16_7symlut_byte", LUT7, 2, 0, false },
+  { "rle24_sym", PLAIN, 3, 1, false }, { "rle24_sym_packed", PACKED, 3, 1, false }, { "rle24_3symlut_sym", LUT3, 3, 1, false }, { "rle24_7symlut_sym", LUT7, 3, 1, false },
+  { "rle24_byte", PLAIN, 3, 0, false }, { "rle24_byte_packed", PACKED, 3, 0, false }, { "rle24_3symlut_byte", LUT3, 3, 0, false }, { "rle24_7symlut_byte", LUT7, 3, 0, false },
+  { "rle32_sym", PLAIN, 4, 1, false }, { "rle32_sym_packed", PACKED, 4, 1, false }, { "rle32_3symlut_sym", LUT3, 4, 1, false }, { "rle32_7symlut_sym", LUT7, 4, 1, false },
+  { "rle32_byte", PLAIN, 4, 0, false }, { "rle32_byte_packed", PACKED, 4, 0, false }, { "rle32_3symlut_byte", LUT3, 4, 0, false }, { "rle32_7symlut_byte", LUT7, 4, 0, false },
+  { "rle48_sym", PLAIN, 6, 1, false }, { "rle48_sym_packed", PACKED, 6, 1, false }, { "rle48_3symlut_sym", LUT3, 6, 1, false }, { "rle48_7symlut_sym", LUT7, 6, 1, false },
+  { "rle48_byte", PLAIN, 6, 0, false }, { "rle48_byte_packed", PACKED, 6, 0, false }, { "rle48_3symlut_byte", LUT3, 6, 0, false }, { "rle48_7symlut_byte", LUT7, 6, 0, false },
+  { "rle64_sym", PLAIN, 8, 1, false }, { "rle64_sym_packed", PACKED, 8, 1, false }, { "rle64_3symlut_sym", LUT3, 8, 1, false }, { "rle64_7symlut_sym", LUT7, 8, 1, false },
+  { "rle64_byte", PLAIN, 8, 0, false }, { "rle64_byte_packed", PACKED, 8, 0, false }, { "rle64_3symlut_byte", LUT3, 8, 0, false }, { "rle64_7symlut_byte", LUT7, 8, 0, false },
+  // 128 bit symbols
+  { "rle128_sym", PLAIN, 16, 1, false }, { "rle128_sym_packed", PACKED, 16, 1, false }, { "rle128_byte", PLAIN, 16, 0, false }, { "rle128_byte_packed", PACKED, 16, 0, false },
+  // Short family (reference: src/rle.h:202-348, src/codec_funcs.h:283-388)
+  { "rle8_multi_short", SHORT0, 1, 0, false }, { "rle8_1symlut_short", SHORT1, 1, 0, false }, { "rle8_3symlut_short", SHORT3, 1, 0, false }, { "rle8_7symlut_short", SHORT7, 1, 0, false },
+  { "rle16_sym_short", SHORT0, 2, 1, false }, { "rle16_1symlut_sym_short", SHORT1, 2, 1, false }, { "rle16_3symlut_sym_short", SHORT3, 2, 1, false }, { "rle16_7symlut_sym_short", SHORT7, 2, 1, false },
+  { "rle16_byte_short", SHORT0, 2, 0, false }, { "rle16_1symlut_byte_short", SHORT1, 2, 0, false }, { "rle16_3symlut_byte_short", SHORT3, 2, 0, false }, { "rle16_7symlut_byte_short", SHORT7, 2, 0, false },
+  { "rle24_sym_short", SHORT0, 3, 1, false }, { "rle24_1symlut_sym_short", SHORT1, 3, 1, false }, { "rle24_3symlut_sym_short", SHORT3, 3, 1, false }, { "rle24_7symlut_sym_short", SHORT7, 3, 1, false },
+  { "rle24_byte_short", SHORT0, 3, 0, false }, { "rle24_1symlut_byte_short", SHORT1, 3, 0, false }, { "rle24_3symlut_byte_short", SHORT3, 3, 0, false }, { "rle24_7symlut_byte_short", SHORT7, 3, 0, false },
+  { "rle32_sym_short", SHORT0, 4, 1, false }, { "rle32_1symlut_sym_short", SHORT1, 4, 1, false }, { "rle32_3symlut_sym_short", SHORT3, 4, 1, false }, { "rle32_7symlut_sym_short", SHORT7, 4, 1, false },
+  { "rle32_byte_short", SHORT0, 4, 0, false }, { "rle32_1symlut_byte_short", SHORT1, 4, 0, false }, { "rle32_3symlut_byte_short", SHORT3, 4, 0, false }, { "rle32_7symlut_byte_short", SHORT7, 4, 0, false },
+  { "rle48_sym_short", SHORT0, 6, 1, false }, { "rle48_1symlut_sym_short", SHORT1, 6, 1, false }, { "rle48_3symlut_sym_short", SHORT3, 6, 1, false }, { "rle48_7symlut_sym_short", SHORT7, 6, 1, false },
+  { "rle48_byte_short", SHORT0, 6, 0, false }, { "rle48_1symlut_byte_short", SHORT1, 6, 0, false }, { "rle48_3symlut_byte_short", SHORT3, 6, 0, false }, { "rle48_7symlut_byte_short", SHORT7, 6, 0, false },
+  { "rle64_sym_short", SHORT0, 8, 1, false }, { "rle64_1symlut_sym_short", SHORT1, 8, 1, false }, { "rle64_3symlut_sym_short", SHORT3, 8, 1, false }, { "rle64_7symlut_sym_short", SHORT7, 8, 1, false },
+  { "rle64_byte_short", SHORT0, 8, 0, false }, { "rle64_1symlut_byte_short", SHORT1, 8, 0, false }, { "rle64_3symlut_byte_short", SHORT3, 8, 0, false }, { "rle64_7symlut_byte_short", SHORT7, 8, 0, false },
+  // Greedy encoders (reference: src/rle.h:398-416); the decode side is the Short decoder of the same grammar
+  { "rle16_1symlut_byte_short_greedy", SHORT1, 2, 0, true }, { "rle16_3symlut_byte_short_greedy", SHORT3, 2, 0, true }, { "rle16_7symlut_byte_short_greedy", SHORT7, 2, 0, true },
+  { "rle24_1symlut_byte_short_greedy", SHORT1, 3, 0, true }, { "rle24_3symlut_byte_short_greedy", SHORT3, 3, 0, true }, { "rle24_7symlut_byte_short_greedy", SHORT7, 3, 0, true },
+  { "rle32_1symlut_byte_short_greedy", SHORT1, 4, 0, true }, { "rle32_3symlut_byte_short_greedy", SHORT3, 4, 0, true }, { "rle32_7symlut_byte_short_greedy", SHORT7, 4, 0, true },
+  { "rle48_1symlut_byte_short_greedy", SHORT1, 6, 0, true }, { "rle48_3symlut_byte_short_greedy", SHORT3, 6, 0, true }, { "rle48_7symlut_byte_short_greedy", SHORT7, 6, 0, true },
+  { "rle64_1symlut_byte_short_greedy", SHORT1, 8, 0, true }, { "rle64_3symlut_byte_short_greedy", SHORT3, 8, 0, true }, { "rle64_7symlut_byte_short_greedy", SHORT7, 8, 0, true },
+  // one symbol per stream, none in the packets (src/rle.h:223-224)
+  { "rle8_single_short", SHORT_SINGLE, 1, 0, false },
+};
+
+inline int codec_id_not_in_table() { return -1; }   // (not constexpr: to reach it in a constant expression is the compile error)
+constexpr int codec_id(Family fam, int S, int aligned, bool greedy = false)
+{
+  for (int c = 0; c < kCodecCount; c++)
+    if (kCodecs[c].fam == fam && kCodecs[c].S == S && kCodecs[c].aligned == aligned && kCodecs[c].greedy == greedy) return c;
+  return codec_id_not_in_table();
+}
+constexpr int codec_id(int fam, int S, int aligned, bool greedy = false) { return codec_id((Family)fam, S, aligned, greedy); }   // (kernels take FAM as an int)
+
+static_assert(kCodecCount == HSRLE_CODEC_COUNT, "one row per public codec id");
+static_assert(codec_id(PLAIN, 1, 0) == HSRLE_RLE8_MULTI && codec_id(PACKED, 1, 0) == HSRLE_RLE8_PACKED_MULTI && codec_id(LUT3, 1, 0) == HSRLE_RLE8_3SYMLUT &&
+              codec_id(LUT7, 1, 0) == HSRLE_RLE8_7SYMLUT && codec_id(SINGLE, 1, 0) == HSRLE_RLE8_SINGLE && codec_id(PACKED_SINGLE, 1, 0) == HSRLE_RLE8_PACKED_SINGLE, "8 bit ids");
+static_assert(codec_id(PLAIN, 2, 1) == HSRLE_RLE16_SYM && codec_id(PLAIN, 3, 1) == HSRLE_RLE24_SYM && codec_id(PLAIN, 4, 1) == HSRLE_RLE32_SYM && codec_id(PLAIN, 6, 1) == HSRLE_RLE48_SYM &&
+              codec_id(PLAIN, 8, 1) == HSRLE_RLE64_SYM && codec_id(PACKED, 2, 0) == HSRLE_RLE16_BYTE_PACKED && codec_id(LUT3, 4, 1) == HSRLE_RLE32_3SYMLUT_SYM &&
+              codec_id(LUT7, 8, 0) == HSRLE_RLE64_7SYMLUT_BYTE, "2 .. 8 byte symbol ids");
+static_assert(codec_id(PLAIN, 16, 1) == HSRLE_RLE128_SYM && codec_id(PACKED, 16, 1) == HSRLE_RLE128_SYM_PACKED && codec_id(PLAIN, 16, 0) == HSRLE_RLE128_BYTE &&
+              codec_id(PACKED, 16, 0) == HSRLE_RLE128_BYTE_PACKED, "128 bit ids");
+static_assert(codec_id(SHORT0, 1, 0) == HSRLE_RLE8_MULTI_SHORT && codec_id(SHORT1, 1, 0) == HSRLE_RLE8_1SYMLUT_SHORT && codec_id(SHORT3, 1, 0) == HSRLE_RLE8_3SYMLUT_SHORT &&
+              codec_id(SHORT7, 1, 0) == HSRLE_RLE8_7SYMLUT_SHORT && codec_id(SHORT0, 2, 1) == HSRLE_RLE16_SYM_SHORT && codec_id(SHORT0, 3, 1) == HSRLE_RLE24_SYM_SHORT &&
+              codec_id(SHORT0, 4, 1) == HSRLE_RLE32_SYM_SHORT && codec_id(SHORT0, 6, 1) == HSRLE_RLE48_SYM_SHORT && codec_id(SHORT0, 8, 1) == HSRLE_RLE64_SYM_SHORT &&
+              codec_id(SHORT_SINGLE, 1, 0) == HSRLE_RLE8_SINGLE_SHORT, "Short family ids");
+static_assert(codec_id(SHORT1, 2, 0, true) == HSRLE_RLE16_1SYMLUT_BYTE_SHORT_GREEDY && codec_id(SHORT1, 3, 0, true) == HSRLE_RLE24_1SYMLUT_BYTE_SHORT_GREEDY &&
+              codec_id(SHORT1, 4, 0, true) == HSRLE_RLE32_1SYMLUT_BYTE_SHORT_GREEDY && codec_id(SHORT1, 6, 0, true) == HSRLE_RLE48_1SYMLUT_BYTE_SHORT_GREEDY &&
+              codec_id(SHORT1, 8, 0, true) == HSRLE_RLE64_1SYMLUT_BYTE_SHORT_GREEDY, "Greedy ids");
+
+// ---- what the host code asks of a row ----
+constexpr bool is_single(const CodecInfo &c) { return c.fam == SINGLE || c.fam == PACKED_SINGLE || c.fam == SHORT_SINGLE; }   // ONE symbol per stream / block: picked first, its byte follows the header
+constexpr bool is_greedy(const CodecInfo &c) { return c.greedy; }
+constexpr bool is_short(const CodecInfo &c) { return c.fam >= SHORT0; }
+constexpr bool is_lut_header(const CodecInfo &c) { return c.fam == LUT3 || c.fam == LUT7 || is_short(c); }   // 8-byte stream header
+// list length K of the move-to-front list: 0 / 1 / 3 / 7 (hsrle_common.hip.h: Traits::K)
+constexpr int list_len(const CodecInfo &c) { return (c.fam == LUT3 || c.fam == SHORT3) ? 3 : ((c.fam == LUT7 || c.fam == SHORT7) ? 7 : (c.fam == SHORT1 ? 1 : 0)); }
+// symbol-state slots of the codec's decoder (IndexState<FAM>::KE): 0 plain / Single / 0-symbol Short, 1 Packed / 1-symbol list, 3, 7
+constexpr int state_slots(const CodecInfo &c) { return (c.fam == PACKED || c.fam == PACKED_SINGLE) ? 1 : list_len(c); }
+// 9 bytes (a mode byte behind the two sizes) for the 8 bit plain / Packed / Single codecs, 8 elsewhere (Traits::kHeaderSize)
+constexpr uint32_t header_size(const CodecInfo &c) { return (c.S == 1 && !is_lut_header(c)) ? 9u : 8u; }
+// the 7-bit-or-4-byte range field: Packed byte-aligned and 8 bit Packed; sym-aligned Packed is the hybrid (Traits::kRange7)
+constexpr bool range7(const CodecInfo &c) { return c.fam == PACKED && !c.aligned; }
+// the run length every state of the codec's encoder stores (SURVEY.md A.2 LONG / the Short family's SMINL): the monolithic and the split encode cut behind such runs
+constexpr uint32_t cut_long(const CodecInfo &c)
+{
+  const uint32_t S = c.S;
+  // Greedy encoders (rleX_Xsl_short.h:746-1000): a run of SMINL = S + 11 bytes is stored whatever the state -- but the scan may enter a
+  // periodic stretch up to ~2 S bytes late (through a prefix of a listed symbol), so a stretch is a cut from S + 11 + 3 S bytes on
+  if (c.greedy) return 4u * S + 11u;
+  switch (c.fam)
+  {
+  case SHORT_SINGLE: return 27u;                                  // rle8_single_short: runs of THE symbol of SMINL = 11 bytes are always stored; + 16, the body counts a run from where its search found it
+  case SINGLE: return 8u;                                         // 8 bit Single: runs of THE symbol with count >= LONG (rle8_extreme_cpu.h:10-11, :21-23)
+  case PACKED_SINGLE: return 10u;
+  case PLAIN: return S == 1 ? 6u : S + 11u;                       // rle8_extreme_cpu.h:974: count >= 6 whatever the range; rleX_extreme_cpu.h:10-11, rle128_extreme_cpu.h:10-11
+  case PACKED: return S == 1 ? 11u : (c.aligned ? S + 10u : S + 11u);   // rle8_extreme_cpu.h:978 (body) and :122 (tail); sym-aligned Packed: the hybrid of A.5 q10
+  case LUT3: case LUT7: return S + 10u;                           // rleX_Xsl.h:132
+  case SHORT0: return S + 12u;                                    // rleX_Xsl_short.h: always stored from S + 12 on (0-symbol codec)
+  default: return S + 11u;                                        // ... from S + 11 on with a list of 1 / 3 / 7 symbols
+  }
+}
+// the codecs whose encoder state at a cut is fixed by the cut itself (no list, or a one-symbol list = the cut's symbol): plain / Packed / Short without or with a
+// one-symbol list, of 1 .. 8 byte symbols -- the chunks of their monolithic streams go to the windowed position-parallel encoders
+constexpr bool chunk_mode(const CodecInfo &c) { return (c.fam == PLAIN || c.fam == PACKED || c.fam == SHORT0 || c.fam == SHORT1) && c.S <= 8 && !c.greedy; }
+// windowed encoders, blocks of ANY size: plain / Packed of 1 .. 8 byte symbols write 8 or 32 bit fields whatever the block size (hsrle_capi_encode.inc: ppw_applies)
+constexpr bool any_block_windowed(const CodecInfo &c) { return (c.fam == PLAIN || c.fam == PACKED) && c.S <= 8; }
+// Greedy with a list of ONE symbol: behind a stored run the list is that run's symbol, so a chunk's first guess is right (split_encode_applies)
+constexpr bool greedy_one_symbol_list(const CodecInfo &c) { return c.greedy && c.fam == SHORT1; }
+// the codecs that have a many-lane chunk encoder but no run list encoder: small containers of 1 .. 4 KiB blocks take the split encode IF the
+// caller's workspace has its regions (hsrle_compress_workspace_size_codec; the library's own scratch always has)
+constexpr bool split_small(const CodecInfo &c) { return is_single(c) || c.S == 16 || greedy_one_symbol_list(c); }
+
+} // namespace hsrle

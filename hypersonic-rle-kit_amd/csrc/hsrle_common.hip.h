@@ -11,11 +11,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace hsrle {
+#include "hsrle_codecs.h"   // enum Family and the codec table
 
-enum Family : int { PLAIN = 0, PACKED = 1, LUT3 = 2, LUT7 = 3, SINGLE = 4, PACKED_SINGLE = 5,
-                    SHORT0 = 6, SHORT1 = 7, SHORT3 = 8, SHORT7 = 9,     // Short family: 0 / 1 / 3 / 7 symbol LUT, one-byte packed headers
-                    SHORT_SINGLE = 10 };                                // rle8_single_short: one symbol per stream, none in the packets
+namespace hsrle {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));

@@ -1,5 +1,5 @@
 // hsrle_inst_generic.inc -- instantiates the 8 codecs of one symbol width (16/24/32/48/64 bit).
-// Included by inst_wNN.hip with HSRLE_W (bits), HSRLE_S (bytes) and HSRLE_BASE (first codec id) defined.
+// Included by inst_wNN.hip with HSRLE_W (bits) and HSRLE_S (bytes) defined.
 #include "hsrle_decode.hip.h"
 #include "hsrle_encode.hip.h"
 #include "hsrle_encodeS.hip.h"
@@ -120,33 +120,19 @@ static hipError_t menc_greedy7(const EncodeArgs &a, const MonoEncodeArgs &m, hip
 
 void HSRLE_CAT(register_w, HSRLE_W)(DecodeLaunch *dec, EncodeLaunch *enc, IndexLaunch *idx, SubBlockLaunch *sub, MonoEncodeLaunch *menc)
 {
-  dec[HSRLE_BASE + 0] = dec_sym; idx[HSRLE_BASE + 0] = idx_sym; sub[HSRLE_BASE + 0] = sub_sym;         enc[HSRLE_BASE + 0] = enc_sym;
-  dec[HSRLE_BASE + 1] = dec_sym_packed; idx[HSRLE_BASE + 1] = idx_sym_packed; sub[HSRLE_BASE + 1] = sub_sym_packed;  enc[HSRLE_BASE + 1] = enc_sym_packed;
-  dec[HSRLE_BASE + 2] = dec_lut3_sym; idx[HSRLE_BASE + 2] = idx_lut3_sym; sub[HSRLE_BASE + 2] = sub_lut3_sym;    enc[HSRLE_BASE + 2] = enc_lut3_sym;
-  dec[HSRLE_BASE + 3] = dec_lut7_sym; idx[HSRLE_BASE + 3] = idx_lut7_sym; sub[HSRLE_BASE + 3] = sub_lut7_sym;    enc[HSRLE_BASE + 3] = enc_lut7_sym;
-  dec[HSRLE_BASE + 4] = dec_byte; idx[HSRLE_BASE + 4] = idx_byte; sub[HSRLE_BASE + 4] = sub_byte;        enc[HSRLE_BASE + 4] = enc_byte;
-  dec[HSRLE_BASE + 5] = dec_byte_packed; idx[HSRLE_BASE + 5] = idx_byte_packed; sub[HSRLE_BASE + 5] = sub_byte_packed; enc[HSRLE_BASE + 5] = enc_byte_packed;
-  dec[HSRLE_BASE + 6] = dec_lut3_byte; idx[HSRLE_BASE + 6] = idx_lut3_byte; sub[HSRLE_BASE + 6] = sub_lut3_byte;   enc[HSRLE_BASE + 6] = enc_lut3_byte;
-  dec[HSRLE_BASE + 7] = dec_lut7_byte; idx[HSRLE_BASE + 7] = idx_lut7_byte; sub[HSRLE_BASE + 7] = sub_lut7_byte;   enc[HSRLE_BASE + 7] = enc_lut7_byte;
-  menc[HSRLE_BASE + 0] = menc_sym; menc[HSRLE_BASE + 1] = menc_sym_packed; menc[HSRLE_BASE + 4] = menc_byte; menc[HSRLE_BASE + 5] = menc_byte_packed;
-  menc[kShortBaseW + (HSRLE_BASE - 6) + 0] = menc_short0_sym; menc[kShortBaseW + (HSRLE_BASE - 6) + 4] = menc_short0_byte;
-  menc[HSRLE_BASE + 2] = menc_lut3_sym; menc[HSRLE_BASE + 3] = menc_lut7_sym; menc[HSRLE_BASE + 6] = menc_lut3_byte; menc[HSRLE_BASE + 7] = menc_lut7_byte;
-  menc[kShortBaseW + (HSRLE_BASE - 6) + 1] = menc_short1_sym; menc[kShortBaseW + (HSRLE_BASE - 6) + 2] = menc_short3_sym; menc[kShortBaseW + (HSRLE_BASE - 6) + 3] = menc_short7_sym;
-  menc[kShortBaseW + (HSRLE_BASE - 6) + 5] = menc_short1_byte; menc[kShortBaseW + (HSRLE_BASE - 6) + 6] = menc_short3_byte; menc[kShortBaseW + (HSRLE_BASE - 6) + 7] = menc_short7_byte;
-  constexpr int SB = kShortBaseW + (HSRLE_BASE - 6);
-  dec[SB + 0] = dec_short0_sym; idx[SB + 0] = idx_short0_sym; sub[SB + 0] = sub_short0_sym;  enc[SB + 0] = enc_short0_sym;
-  dec[SB + 1] = dec_short1_sym; idx[SB + 1] = idx_short1_sym; sub[SB + 1] = sub_short1_sym;  enc[SB + 1] = enc_short1_sym;
-  dec[SB + 2] = dec_short3_sym; idx[SB + 2] = idx_short3_sym; sub[SB + 2] = sub_short3_sym;  enc[SB + 2] = enc_short3_sym;
-  dec[SB + 3] = dec_short7_sym; idx[SB + 3] = idx_short7_sym; sub[SB + 3] = sub_short7_sym;  enc[SB + 3] = enc_short7_sym;
-  dec[SB + 4] = dec_short0_byte; idx[SB + 4] = idx_short0_byte; sub[SB + 4] = sub_short0_byte; enc[SB + 4] = enc_short0_byte;
-  dec[SB + 5] = dec_short1_byte; idx[SB + 5] = idx_short1_byte; sub[SB + 5] = sub_short1_byte; enc[SB + 5] = enc_short1_byte;
-  dec[SB + 6] = dec_short3_byte; idx[SB + 6] = idx_short3_byte; sub[SB + 6] = sub_short3_byte; enc[SB + 6] = enc_short3_byte;
-  dec[SB + 7] = dec_short7_byte; idx[SB + 7] = idx_short7_byte; sub[SB + 7] = sub_short7_byte; enc[SB + 7] = enc_short7_byte;
-  constexpr int GB = kGreedyBase + 3 * ((HSRLE_BASE - 6) / 8);
-  dec[GB + 0] = dec_short1_byte; idx[GB + 0] = idx_short1_byte; sub[GB + 0] = sub_short1_byte; enc[GB + 0] = enc_greedy1;
-  dec[GB + 1] = dec_short3_byte; idx[GB + 1] = idx_short3_byte; sub[GB + 1] = sub_short3_byte; enc[GB + 1] = enc_greedy3;
-  dec[GB + 2] = dec_short7_byte; idx[GB + 2] = idx_short7_byte; sub[GB + 2] = sub_short7_byte; enc[GB + 2] = enc_greedy7;
-  menc[GB + 0] = menc_greedy1; menc[GB + 1] = menc_greedy3; menc[GB + 2] = menc_greedy7;
+  // one line per codec: the slot of <FAM, HSRLE_S, AL> (hsrle_codecs.h) in every table
+#define HSRLE_REG(FAM, AL, TAG) \
+  { constexpr int c = codec_id(FAM, HSRLE_S, AL); dec[c] = dec_##TAG; idx[c] = idx_##TAG; sub[c] = sub_##TAG; enc[c] = enc_##TAG; menc[c] = menc_##TAG; }
+  HSRLE_REG(PLAIN, 1, sym) HSRLE_REG(PACKED, 1, sym_packed) HSRLE_REG(LUT3, 1, lut3_sym) HSRLE_REG(LUT7, 1, lut7_sym)
+  HSRLE_REG(PLAIN, 0, byte) HSRLE_REG(PACKED, 0, byte_packed) HSRLE_REG(LUT3, 0, lut3_byte) HSRLE_REG(LUT7, 0, lut7_byte)
+  HSRLE_REG(SHORT0, 1, short0_sym) HSRLE_REG(SHORT1, 1, short1_sym) HSRLE_REG(SHORT3, 1, short3_sym) HSRLE_REG(SHORT7, 1, short7_sym)
+  HSRLE_REG(SHORT0, 0, short0_byte) HSRLE_REG(SHORT1, 0, short1_byte) HSRLE_REG(SHORT3, 0, short3_byte) HSRLE_REG(SHORT7, 0, short7_byte)
+#undef HSRLE_REG
+  // Greedy: encoders of their own, the Short decoders of the same grammar
+#define HSRLE_REG_GREEDY(FAM, K) \
+  { constexpr int c = codec_id(FAM, HSRLE_S, 0, true); dec[c] = dec_short##K##_byte; idx[c] = idx_short##K##_byte; sub[c] = sub_short##K##_byte; enc[c] = enc_greedy##K; menc[c] = menc_greedy##K; }
+  HSRLE_REG_GREEDY(SHORT1, 1) HSRLE_REG_GREEDY(SHORT3, 3) HSRLE_REG_GREEDY(SHORT7, 7)
+#undef HSRLE_REG_GREEDY
 }
 
 } // namespace hsrle

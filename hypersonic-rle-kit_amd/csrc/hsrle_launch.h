@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include "hsrle_codecs.h"
 #include "hsrle_ring_probe.hip.h"
 
 namespace hsrle {
@@ -126,11 +127,6 @@ constexpr uint32_t kPpwSStateWords = 16u;                        // ... of the 1
 typedef hipError_t (*DecodeLaunch)(const DecodeArgs &, hipStream_t);
 typedef hipError_t (*EncodeLaunch)(const EncodeArgs &, hipStream_t);
 
-constexpr int kSingleShort = 109;                 // rle8_single_short
-constexpr int kCodecCount = 110;                 // 50 extreme codecs + 44 of the Short family + 15 Greedy encoders (8f-1)
-constexpr int kGreedyBase = 94;                   // + 3 * index(W in 16,24,32,48,64) + {0 1symlut, 1 3symlut, 2 7symlut}: rle{W}_{K}symlut_byte_short_compress_greedy
-constexpr int kShortBase8 = 50;                   // rle8_multi_short, rle8_{1,3,7}symlut_short
-constexpr int kShortBaseW = 54;                   // + 8 * index(W in 16,24,32,48,64) + {0 sym, 1 1symlut_sym, 2 3symlut_sym, 3 7symlut_sym, 4 byte, 5 1symlut_byte, 6 3symlut_byte, 7 7symlut_byte}
 constexpr uint32_t kEncodeLdsCap = 20000;       // bytes of dynamic LDS per encode workgroup (0 = no residency cap); tuned on MI355X
 #ifndef HSRLE_DECODE_TILE
 #define HSRLE_DECODE_TILE 128
@@ -147,7 +143,7 @@ constexpr int kDecodeRing = HSRLE_DECODE_RING; // per-lane stream ring in LDS (k
 
 void register_w8(DecodeLaunch *dec, EncodeLaunch *enc, IndexLaunch *idx, SubBlockLaunch *sub, MonoEncodeLaunch *menc, WaveEncodeLaunch *wenc);
 void register_pp8(PpLaunch *pp);
-void register_pp8w(PpwLaunch *ppw);   // [0] rle8_multi, [1] rle8_packed_multi
+void register_pp8w(PpwLaunch *ppw);   // [codec id]: rle8_multi, rle8_packed_multi
 void register_ppLw(PpwLaunch *ppw);   // [codec id]: the codecs of hsrle_encodeLp.hip.h, blocks above 4 KiB
 void register_ppSw(PpwLaunch *ppw);   // [codec id]: the codecs of hsrle_encodeSp.hip.h, blocks above 4 KiB
 void register_ppSwM(PpwLaunch *ppw);  // [codec id]: their chunk mode (the chunks of one monolithic stream), the 42 codecs the cut fixes the state of

@@ -21,10 +21,10 @@ static hipError_t pp128_launch(const PpArgs &a, int phase, hipStream_t st)
 
 void register_pp128(PpLaunch *pp)
 {
-  pp[46] = pp128_launch<false, 1>;   // rle128_sym
-  pp[47] = pp128_launch<true, 1>;    // rle128_sym_packed
-  pp[48] = pp128_launch<false, 0>;   // rle128_byte
-  pp[49] = pp128_launch<true, 0>;    // rle128_byte_packed
+  pp[codec_id(PLAIN, 16, 1)] = pp128_launch<false, 1>;
+  pp[codec_id(PACKED, 16, 1)] = pp128_launch<true, 1>;
+  pp[codec_id(PLAIN, 16, 0)] = pp128_launch<false, 0>;
+  pp[codec_id(PACKED, 16, 0)] = pp128_launch<true, 0>;
 }
 
 } // namespace hsrle

@@ -21,8 +21,8 @@ static hipError_t pp_launch(const PpArgs &a, int phase, hipStream_t st)
 
 void register_pp8(PpLaunch *pp)
 {
-  pp[0] = pp_launch<PLAIN>;
-  pp[1] = pp_launch<PACKED>;
+  pp[codec_id(PLAIN, 1, 0)] = pp_launch<PLAIN>;
+  pp[codec_id(PACKED, 1, 0)] = pp_launch<PACKED>;
 }
 
 } // namespace hsrle

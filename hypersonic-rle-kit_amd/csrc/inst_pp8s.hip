@@ -21,9 +21,9 @@ static hipError_t pps_launch(const PpArgs &a, int phase, hipStream_t st)
 
 void register_pp8s(PpLaunch *pp)
 {
-  pp[4] = pps_launch<0>;               // rle8_single
-  pp[5] = pps_launch<1>;               // rle8_packed_single
-  pp[kSingleShort] = pps_launch<2>;    // rle8_single_short
+  pp[codec_id(SINGLE, 1, 0)] = pps_launch<0>;
+  pp[codec_id(PACKED_SINGLE, 1, 0)] = pps_launch<1>;
+  pp[codec_id(SHORT_SINGLE, 1, 0)] = pps_launch<2>;
 }
 
 } // namespace hsrle

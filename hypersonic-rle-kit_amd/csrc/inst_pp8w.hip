@@ -17,8 +17,8 @@ static hipError_t ppw_launch(const PpwArgs &a, int phase, hipStream_t st)
 
 void register_pp8w(PpwLaunch *ppw)
 {
-  ppw[0] = ppw_launch<PLAIN>;
-  ppw[1] = ppw_launch<PACKED>;
+  ppw[codec_id(PLAIN, 1, 0)] = ppw_launch<PLAIN>;
+  ppw[codec_id(PACKED, 1, 0)] = ppw_launch<PACKED>;
 }
 
 } // namespace hsrle

@@ -45,13 +45,14 @@ static hipError_t menc_any(const EncodeArgs &a, const MonoEncodeArgs &m, hipStre
 
 void register_w128(DecodeLaunch *dec, EncodeLaunch *enc, IndexLaunch *idx, SubBlockLaunch *sub, MonoEncodeLaunch *menc)
 {
-  menc[46] = menc_any<PLAIN, 1>; menc[47] = menc_any<PACKED, 1>; menc[48] = menc_any<PLAIN, 0>; menc[49] = menc_any<PACKED, 0>;
-  sub[46] = sub_sym; sub[47] = sub_sym_packed; sub[48] = sub_byte; sub[49] = sub_byte_packed;
-  idx[46] = idx_sym; idx[47] = idx_sym_packed; idx[48] = idx_byte; idx[49] = idx_byte_packed;
-  dec[46] = dec_sym;         enc[46] = enc_sym;
-  dec[47] = dec_sym_packed;  enc[47] = enc_sym_packed;
-  dec[48] = dec_byte;        enc[48] = enc_byte;
-  dec[49] = dec_byte_packed; enc[49] = enc_byte_packed;
+  constexpr int sym = codec_id(PLAIN, 16, 1), symPacked = codec_id(PACKED, 16, 1), byte = codec_id(PLAIN, 16, 0), bytePacked = codec_id(PACKED, 16, 0);
+  menc[sym] = menc_any<PLAIN, 1>; menc[symPacked] = menc_any<PACKED, 1>; menc[byte] = menc_any<PLAIN, 0>; menc[bytePacked] = menc_any<PACKED, 0>;
+  sub[sym] = sub_sym; sub[symPacked] = sub_sym_packed; sub[byte] = sub_byte; sub[bytePacked] = sub_byte_packed;
+  idx[sym] = idx_sym; idx[symPacked] = idx_sym_packed; idx[byte] = idx_byte; idx[bytePacked] = idx_byte_packed;
+  dec[sym] = dec_sym;               enc[sym] = enc_sym;
+  dec[symPacked] = dec_sym_packed;  enc[symPacked] = enc_sym_packed;
+  dec[byte] = dec_byte;             enc[byte] = enc_byte;
+  dec[bytePacked] = dec_byte_packed; enc[bytePacked] = enc_byte_packed;
 }
 
 } // namespace hsrle

@@ -175,31 +175,26 @@ static hipError_t wenc_packed(const WaveEncodeArgs &a, hipStream_t st) { return 
 void register_w8(DecodeLaunch *dec, EncodeLaunch *enc, IndexLaunch *idx, SubBlockLaunch *sub, MonoEncodeLaunch *menc, WaveEncodeLaunch *wenc)
 {
 #ifdef HSRLE_EXPERIMENTS
-  wenc[0] = wenc_plain; wenc[1] = wenc_packed;
+  wenc[codec_id(PLAIN, 1, 0)] = wenc_plain; wenc[codec_id(PACKED, 1, 0)] = wenc_packed;
 #else
   (void)wenc;
 #endif
-  menc[4] = menc_single_any<false>; menc[5] = menc_single_any<true>; menc[kSingleShort] = menc_single_short;
-  menc[0] = menc_plain; menc[1] = menc_packed; menc[kShortBase8 + 0] = menc_short0;
-  menc[2] = menc_lut3; menc[3] = menc_lut7; menc[kShortBase8 + 1] = menc_short1; menc[kShortBase8 + 2] = menc_short3; menc[kShortBase8 + 3] = menc_short7;
-  sub[0] = sub_plain; sub[1] = sub_packed; sub[2] = sub_lut3; sub[3] = sub_lut7; sub[4] = sub_plain_any; sub[5] = sub_packed_any;
-  sub[kShortBase8 + 0] = sub_short0; sub[kShortBase8 + 1] = sub_short1; sub[kShortBase8 + 2] = sub_short3; sub[kShortBase8 + 3] = sub_short7;
-  sub[kSingleShort] = sub_short_single;
-  idx[0] = idx_plain; idx[1] = idx_packed; idx[2] = idx_lut3; idx[3] = idx_lut7; idx[4] = idx_plain; idx[5] = idx_packed;
-  idx[kShortBase8 + 0] = idx_short0; idx[kShortBase8 + 1] = idx_short1; idx[kShortBase8 + 2] = idx_short3; idx[kShortBase8 + 3] = idx_short7;
-  idx[kSingleShort] = idx_short_single;
-  dec[0] = dec_plain;  enc[0] = enc_plain;
-  dec[1] = dec_packed; enc[1] = enc_packed;
-  dec[2] = dec_lut3;   enc[2] = enc_lut3;
-  dec[3] = dec_lut7;   enc[3] = enc_lut7;
-  dec[4] = dec_plain_any;  enc[4] = enc_single;
-  dec[5] = dec_packed_any; enc[5] = enc_packed_single;
-  // Short family (rle8_multi_short, rle8_{1,3,7}symlut_short; reference: src/rle.h:202-222)
-  dec[kShortBase8 + 0] = dec_short0; enc[kShortBase8 + 0] = enc_short0;
-  dec[kShortBase8 + 1] = dec_short1; enc[kShortBase8 + 1] = enc_short1;
-  dec[kShortBase8 + 2] = dec_short3; enc[kShortBase8 + 2] = enc_short3;
-  dec[kShortBase8 + 3] = dec_short7; enc[kShortBase8 + 3] = enc_short7;
-  dec[kSingleShort] = dec_short_single; enc[kSingleShort] = enc_short_single;   // rle8_single_short (src/rle.h:223-224)
+  // one line per codec: the slot of <FAM, 1, 0> (hsrle_codecs.h) in every table.  The Single ids decode with the multi kernels' general form.
+#define HSRLE_REG8(FAM, DEC, ENC, IDX, SUB, MENC) \
+  { constexpr int c = codec_id(FAM, 1, 0); dec[c] = DEC; enc[c] = ENC; idx[c] = IDX; sub[c] = SUB; menc[c] = MENC; }
+  HSRLE_REG8(PLAIN, dec_plain, enc_plain, idx_plain, sub_plain, menc_plain)
+  HSRLE_REG8(PACKED, dec_packed, enc_packed, idx_packed, sub_packed, menc_packed)
+  HSRLE_REG8(LUT3, dec_lut3, enc_lut3, idx_lut3, sub_lut3, menc_lut3)
+  HSRLE_REG8(LUT7, dec_lut7, enc_lut7, idx_lut7, sub_lut7, menc_lut7)
+  HSRLE_REG8(SINGLE, dec_plain_any, enc_single, idx_plain, sub_plain_any, menc_single_any<false>)
+  HSRLE_REG8(PACKED_SINGLE, dec_packed_any, enc_packed_single, idx_packed, sub_packed_any, menc_single_any<true>)
+  // Short family (rle8_multi_short, rle8_{1,3,7}symlut_short; reference: src/rle.h:202-222) and rle8_single_short (src/rle.h:223-224)
+  HSRLE_REG8(SHORT0, dec_short0, enc_short0, idx_short0, sub_short0, menc_short0)
+  HSRLE_REG8(SHORT1, dec_short1, enc_short1, idx_short1, sub_short1, menc_short1)
+  HSRLE_REG8(SHORT3, dec_short3, enc_short3, idx_short3, sub_short3, menc_short3)
+  HSRLE_REG8(SHORT7, dec_short7, enc_short7, idx_short7, sub_short7, menc_short7)
+  HSRLE_REG8(SHORT_SINGLE, dec_short_single, enc_short_single, idx_short_single, sub_short_single, menc_single_short)
+#undef HSRLE_REG8
 }
 
 } // namespace hsrle

@@ -1,0 +1,76 @@
+"""csrc/hsrle_codecs.h against an independent table: a small host program (plain g++, no HIP) prints every row of kCodecs and what the accessors derive from
+it; name, family, symbol bytes and alignment must be those of hsrle_testlib.CODECS (built from the reference's naming scheme, not from the header), the list
+length the one the name states, codec_id() the inverse of the table, and the stream header 9 bytes for the four 8 bit plain / Packed codecs and 8 elsewhere."""
+import os
+import re
+import subprocess
+
+import pytest
+
+import hsrle_testlib as T
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(REPO, "hypersonic-rle-kit_amd", "csrc", "hsrle_codecs.h")
+
+PROGRAM = r"""
+#include "%s"
+#include <stdio.h>
+using namespace hsrle;
+int main()
+{
+  for (int c = 0; c < kCodecCount; c++)
+  {
+    const CodecInfo &i = kCodecs[c];
+    printf("%%d %%s %%d %%d %%d %%d %%d %%d %%u %%u %%d\n", c, i.name, (int)i.fam, (int)i.S, (int)i.aligned, (int)i.greedy, list_len(i), state_slots(i), header_size(i), cut_long(i),
+           codec_id(i.fam, i.S, i.aligned, i.greedy));
+  }
+  return 0;
+}
+"""
+
+# hsrle_testlib family -> (Family value in the header, greedy flag): the Greedy encoders are rows of SHORT1 / 3 / 7 with the flag set
+FAMILY = {T.PLAIN: (0, 0), T.PACKED: (1, 0), T.LUT3: (2, 0), T.LUT7: (3, 0), T.SINGLE: (4, 0), T.PACKED_SINGLE: (5, 0), T.SHORT0: (6, 0), T.SHORT1: (7, 0),
+          T.SHORT3: (8, 0), T.SHORT7: (9, 0), T.GREEDY1: (7, 1), T.GREEDY3: (8, 1), T.GREEDY7: (9, 1), T.SINGLE_SHORT: (10, 0)}
+
+
+@pytest.fixture(scope="module")
+def rows(tmp_path_factory):
+    d = tmp_path_factory.mktemp("codec_traits")
+    src, exe = d / "traits.cpp", d / "traits"
+    src.write_text(PROGRAM % HEADER)
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", str(src), "-o", str(exe)])
+    out = subprocess.check_output([str(exe)], text=True)
+    keys = ("id", "name", "fam", "S", "aligned", "greedy", "K", "slots", "header", "cut", "found")
+    return [{k: (v if k == "name" else int(v)) for k, v in zip(keys, line.split())} for line in out.splitlines()]
+
+
+def test_one_row_per_codec_in_id_order(rows):
+    assert len(rows) == len(T.CODECS) == 110
+    assert [r["id"] for r in rows] == list(range(110))
+
+
+def test_rows_are_the_test_tables(rows):
+    for r, c in zip(rows, T.CODECS):
+        fam, greedy = FAMILY[c.family]
+        assert (r["name"], r["fam"], r["S"], r["aligned"], r["greedy"]) == (c.key, fam, c.S, c.aligned, greedy), c.key
+
+
+def test_list_length_is_what_the_name_says(rows):
+    for r in rows:
+        m = re.search(r"(\d)symlut", r["name"])
+        assert r["K"] == (int(m.group(1)) if m else 0), r["name"]
+        assert r["slots"] == (1 if "packed" in r["name"] else r["K"]), r["name"]   # a Packed decoder keeps the last symbol, a list codec its list
+
+
+def test_codec_id_finds_every_row(rows):
+    assert [r["found"] for r in rows] == list(range(110))
+
+
+def test_header_size(rows):
+    nine = {"rle8_multi", "rle8_packed_multi", "rle8_single", "rle8_packed_single"}
+    for r in rows:
+        assert r["header"] == (9 if r["name"] in nine else 8), r["name"]
+
+
+def test_every_codec_has_a_cut_length(rows):
+    assert all(r["cut"] > r["S"] for r in rows)

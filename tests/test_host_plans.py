@@ -1,0 +1,31 @@
+"""The host side plans what it planned before the codec traits table (csrc/hsrle_codecs.h) replaced the codec-id arithmetic: tools/dump_host_plans.py over
+the current build against tests/golden/host_plans.json, which the same tool wrote from the build of the commit before -- encode path, container / monolithic
+encode and decode workspaces, index size and index workspace, for all 110 codecs over a grid of sizes, block sizes, compressed sizes and record spacings.
+No device is touched."""
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "tools"))
+GOLDEN = os.path.join(REPO, "tests", "golden", "host_plans.json")
+
+
+def test_host_plans_are_the_recorded_ones():
+    import dump_host_plans
+
+    if not os.path.exists(dump_host_plans.LIB):
+        import subprocess
+
+        subprocess.check_call(["make", "-s", "-j8", "-C", os.path.join(REPO, "hypersonic-rle-kit_amd")])
+    with open(GOLDEN) as f:
+        want = json.load(f)
+    got = dump_host_plans.dump(dump_host_plans.load())
+    assert got["grid"] == want["grid"]
+    got, want = dump_host_plans.expand(got["results"]), dump_host_plans.expand(want["results"])
+    assert sorted(got) == sorted(want)
+    for fn, per_codec in want.items():
+        assert list(got[fn]) == list(per_codec), f"{fn}: codec names or their order differ"
+        assert len(per_codec) == 110
+        for name, values in per_codec.items():
+            assert got[fn][name] == values, f"{fn}({name})"

@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""What the device-free planning entry points of libhsrle_hip.so return, for every codec over a fixed grid: the host side's behaviour as data.
+
+  python tools/dump_host_plans.py [out.json]        (HSRLE_LIB=<path> picks another build of the library)
+
+tests/golden/host_plans.json is this tool's output for the build the codec traits table (csrc/hsrle_codecs.h) replaced;
+tests/test_host_plans.py asserts that the current build reproduces it value for value.  None of the calls below touches a device.
+hsrle_mono_tuning() is never called: the plans are those of the defaults.
+"""
+import ctypes
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.environ.get("HSRLE_LIB", os.path.join(REPO, "hypersonic-rle-kit_amd", "libhsrle_hip.so"))
+
+SIZES32 = [4096, (1 << 20) + 128, 88473600, 1 << 30]
+SIZES64 = SIZES32 + [8 << 30]
+BLOCKS = [128, 1024, 4096, 4224, 8192, 65536, 1 << 20]
+SPACINGS = [0, 512, 4096]
+
+
+def compressed_sizes(U):
+    return [U // 8, U]
+
+
+def load(path=LIB):
+    L = ctypes.CDLL(path)
+    u32, u64, ci = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
+    L.hsrle_codec_name.restype = ctypes.c_char_p
+    L.hsrle_codec_name.argtypes = [ci]
+    L.hsrle_encode_path.restype = ci
+    L.hsrle_encode_path.argtypes = [ci, u64, u32]
+    for name, args in (("hsrle_compress_workspace_size_codec", [ci, u64, u32]), ("hsrle_compress_mono_workspace_size", [ci, u32]),
+                       ("hsrle_decompress_mono_workspace_size", [ci, u32, u32]), ("hsrle_mono_index_size", [ci, u32, u32, u32]),
+                       ("hsrle_mono_index_workspace_size", [ci, u32, u32, u32])):
+        getattr(L, name).restype = u64
+        getattr(L, name).argtypes = args
+    return L
+
+
+def dump(L):
+    """{entry point: {"vectors": the distinct value lists in grid order, "codec": {codec name: which of them}}} -- most codecs share a plan"""
+    names = []
+    while True:
+        nm = L.hsrle_codec_name(len(names))
+        if nm is None:
+            break
+        names.append(nm.decode())
+    calls = {
+        "hsrle_encode_path": lambda c: [L.hsrle_encode_path(c, U, B) for U in SIZES64 for B in BLOCKS],
+        "hsrle_compress_workspace_size_codec": lambda c: [L.hsrle_compress_workspace_size_codec(c, U, B) for U in SIZES64 for B in BLOCKS],
+        "hsrle_compress_mono_workspace_size": lambda c: [L.hsrle_compress_mono_workspace_size(c, U) for U in SIZES32],
+        "hsrle_decompress_mono_workspace_size": lambda c: [L.hsrle_decompress_mono_workspace_size(c, U, C) for U in SIZES32 for C in compressed_sizes(U)],
+        "hsrle_mono_index_size": lambda c: [L.hsrle_mono_index_size(c, U, C, sp) for U in SIZES32 for C in compressed_sizes(U) for sp in SPACINGS],
+        "hsrle_mono_index_workspace_size": lambda c: [L.hsrle_mono_index_workspace_size(c, U, C, sp) for U in SIZES32 for C in compressed_sizes(U) for sp in SPACINGS],
+    }
+    out = {}
+    for fn, call in calls.items():
+        vectors, which = [], {}
+        for c, nm in enumerate(names):
+            v = call(c)
+            if v not in vectors:
+                vectors.append(v)
+            which[nm] = vectors.index(v)
+        out[fn] = {"vectors": vectors, "codec": which}
+    return {"grid": {"sizes32": SIZES32, "sizes64": SIZES64, "blocks": BLOCKS, "compressed": ["U/8", "U"], "spacings": SPACINGS}, "results": out}
+
+
+def expand(results):
+    """{entry point: {codec name: values}}"""
+    return {fn: {nm: r["vectors"][k] for nm, k in r["codec"].items()} for fn, r in results.items()}
+
+
+if __name__ == "__main__":
+    d = dump(load())
+    # one line per entry point and part: short enough to read, few enough lines to review
+    rows = ['  "%s": {"vectors": %s,\n    "codec": %s}' % (fn, json.dumps(r["vectors"], separators=(",", ":")), json.dumps(r["codec"], separators=(",", ":"))) for fn, r in d["results"].items()]
+    text = '{"grid": %s,\n "results": {\n%s\n }}' % (json.dumps(d["grid"]), ",\n".join(rows))
+    if len(sys.argv) > 1:
+        with open(sys.argv[1], "w") as f:
+            f.write(text + "\n")
+    else:
+        print(text)
