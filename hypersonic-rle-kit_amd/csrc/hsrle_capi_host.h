@@ -1,0 +1,196 @@
+// hsrle_capi_host.h -- part of hsrle_capi.hip: launch tables, the size helpers every plan uses, per-device state and scratch pool, the drop-in calls' staging
+#pragma once
+#include "../../include/hsrle.h"
+#include "hsrle_common.hip.h"
+#include "hsrle_launch.h"
+#include <stdlib.h>
+#include <string.h>
+#include <atomic>
+#include <mutex>
+
+namespace hsrle {
+
+static DecodeLaunch g_dec[kCodecCount];
+static EncodeLaunch g_enc[kCodecCount];
+static IndexLaunch g_idx[kCodecCount];
+static SubBlockLaunch g_sub[kCodecCount];
+static MonoEncodeLaunch g_menc[kCodecCount];
+static WaveEncodeLaunch g_wenc[kCodecCount];
+static PpwLaunch g_ppwL[kCodecCount];               // ... and those of hsrle_encodeLp.hip.h (hsrle_encodeLpw.hip.h)
+static PpwLaunch g_ppwS[kCodecCount];               // ... and the codecs of hsrle_encodeSp.hip.h (hsrle_encodeSpw.hip.h), by codec id
+static PpwLaunch g_ppw[kCodecCount];               // ... for units of any length (hsrle_encode8pw.hip.h), by codec id: rle8_multi, rle8_packed_multi
+static PpwLaunch g_ppwSM[kCodecCount];              // ... the chunk mode of hsrle_encodeSpw.hip.h (the chunks of one monolithic stream), by codec id: 42 codecs
+static PpLaunch g_pp[kCodecCount];                  // position-parallel encoders (hsrle_encode8p.hip.h)
+static std::once_flag g_tableOnce;
+
+static void init_tables()
+{
+  std::call_once(g_tableOnce, [] {
+    register_w8(g_dec, g_enc, g_idx, g_sub, g_menc, g_wenc);
+    register_pp8(g_pp);
+    register_pp8w(g_ppw);
+    register_ppSw(g_ppwS);
+    register_ppSwM(g_ppwSM);
+    register_ppLw(g_ppwL);
+    register_pp8s(g_pp);
+    register_pp128(g_pp);
+    register_ppL(g_pp);
+    register_ppS(g_pp);
+    register_w16(g_dec, g_enc, g_idx, g_sub, g_menc);
+    register_w24(g_dec, g_enc, g_idx, g_sub, g_menc);
+    register_w32(g_dec, g_enc, g_idx, g_sub, g_menc);
+    register_w48(g_dec, g_enc, g_idx, g_sub, g_menc);
+    register_w64(g_dec, g_enc, g_idx, g_sub, g_menc);
+    register_w128(g_dec, g_enc, g_idx, g_sub, g_menc);
+  });
+}
+
+static inline uint32_t bounds32(uint32_t n) { return (n > (1u << 30)) ? 0u : n + (16 + 4 + 1 + 4 + 1 + 64) * 2 + (3 * 4) + 1; }
+static inline uint32_t slot_stride(uint32_t B) { return (bounds32(B) + 15u) & ~15u; }
+static inline uint64_t block_count(uint64_t U, uint32_t B) { return (U + B - 1) / B; }
+static inline uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
+
+static uint32_t env_u32(const char *name, uint32_t dflt) { return knob_u32(name, dflt); }   // (developer knobs: -DHSRLE_EXPERIMENTS builds only, hsrle_launch.h)
+static uint32_t pow2_floor(uint64_t v) { uint32_t r = 1; while ((uint64_t)r * 2u <= v && r < 0x80000000u) r *= 2u; return r; }
+
+static bool valid_block_size(uint32_t B) { return B >= HSRLE_MIN_BLOCK_SIZE && B <= HSRLE_MAX_BLOCK_SIZE && (B % 128u) == 0; }
+
+// ------------------------------------------------------------------------------------------------------------------
+// device state
+
+// Per DEVICE (hipGetDevice() of the calling thread): the staging buffers of the host-pointer drop-in functions.  A drop-in call holds
+// the device's mutex from its first copy to its last, so concurrent drop-in calls on one device run one after the other (the reference's
+// own callers are single threaded: src/main.c, src/rle_fuzz.c); calls on different devices do not meet.  The device-pointer API keeps NO
+// library-owned state between calls: what it needs beyond the caller's buffers is allocated stream-ordered (hipMallocAsync on the
+// caller's stream) for the duration of the call.
+constexpr int kMaxDevices = 64;
+enum WsKind { kCodecWs, kMonoWs };   // which drop-in workspace: rle8m and low-entropy share DeviceState::ws, the monolithic codecs have monoWs (peak device memory: the larger, not the sum)
+struct DeviceState
+{
+  std::mutex mu;
+  void *ws = nullptr, *monoWs = nullptr;   // drop-in workspaces (WsKind)
+  uint64_t wsSize = 0, monoWsSize = 0;
+  hipStream_t aux = nullptr;   // second stream of the chunked compression
+  hipMemPool_t pool = nullptr; // the library's OWN stream-ordered pool on this device (scratch_alloc): the application's default pool is never touched
+  bool poolTried = false;
+  void *monoIn = nullptr, *monoOut = nullptr, *monoAux = nullptr; // staging of the drop-in (host pointer) path
+  uint64_t monoInSize = 0, monoOutSize = 0;
+};
+
+static DeviceState g_devs[kMaxDevices];
+static std::once_flag g_deviceOnce;
+static int g_deviceCount = 0;
+
+static bool device_ok()
+{
+  std::call_once(g_deviceOnce, [] {
+    int n = 0;
+    g_deviceCount = (hipGetDeviceCount(&n) == hipSuccess && n > 0) ? n : 0;
+  });
+  return g_deviceCount > 0;
+}
+
+static DeviceState &this_device()
+{
+  int d = 0;
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDevices) d = 0;
+  return g_devs[d];
+}
+
+// Scratch for the duration of one call on `st`: stream-ordered, so concurrent calls on other streams (or threads) never share it.  It
+// comes from a pool the LIBRARY owns (one per device, created on first use): freed scratch stays in that pool up to the retention set
+// with hsrle_scratch_retention() (default 2 GiB: the small per-call scratch of decode / info calls is never given back and re-mapped;
+// the 9 GB workspace of an 8 GiB compression without a caller's workspace is) and hsrle_trim() hands all of it back.  Round 2 raised the
+// release threshold of the device's DEFAULT pool instead, which kept gigabytes away from the host application's own allocator.
+static std::atomic<uint64_t> g_scratchRetention{ 2ull << 30 };
+static hipMemPool_t device_pool()
+{
+  DeviceState &D = this_device();
+  std::lock_guard<std::mutex> lock(D.mu);
+  if (!D.poolTried)
+  {
+    D.poolTried = true;
+    int d = 0;
+    hipMemPoolProps props = {};
+    props.allocType = hipMemAllocationTypePinned;
+    props.handleTypes = hipMemHandleTypeNone;
+    props.location.type = hipMemLocationTypeDevice;
+    props.location.id = (hipGetDevice(&d) == hipSuccess) ? d : 0;
+    hipMemPool_t pool = nullptr;
+    if (hipMemPoolCreate(&pool, &props) == hipSuccess)
+    {
+      uint64_t keep = g_scratchRetention.load();
+      (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
+      D.pool = pool;
+    }
+    else
+      (void)hipGetLastError();
+  }
+  return D.pool;
+}
+static void *scratch_alloc(uint64_t bytes, hipStream_t st)
+{
+  void *p = nullptr;
+  hipMemPool_t pool = device_pool();
+  if (pool != nullptr && hipMallocFromPoolAsync(&p, bytes, pool, st) == hipSuccess) return p;
+  (void)hipGetLastError();
+  if (hipMallocAsync(&p, bytes, st) == hipSuccess) return p;           // (no pool of our own on this runtime: the default pool, untouched)
+  (void)hipGetLastError();
+  return nullptr;
+}
+static void scratch_free(void *p, hipStream_t st) { if (p) (void)hipFreeAsync(p, st); }
+
+static bool grow(void **p, uint64_t *have, uint64_t need)
+{
+  if (*have >= need && *p)
+    return true;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *have = 0;
+  if (hipMalloc(p, need) != hipSuccess)
+    return false;
+  *have = need;
+  return true;
+}
+
+// One host-pointer drop-in call (hsrle_capi_dropin.h): holds the device's mutex from its construction -- in front of the first copy -- to the end of the
+// call, and hands out the device's staging buffers.  Every family stages through this one sequence: reserve, copy up, enqueue, read words, copy down.
+// (hsrle_compress_host / hsrle_decompress_host allocate and free per call: another contract, not staged here.)
+struct Staging
+{
+  DeviceState &D;
+  std::lock_guard<std::mutex> lock;
+  uint8_t *in = nullptr, *out = nullptr, *ws = nullptr;
+  uint64_t wsSize = 0;
+  uint32_t *status = nullptr;          // the device's status words (256 bytes, allocated with the first call's buffers; the words at + 64)
+
+  Staging() : D(this_device()), lock(D.mu) {}
+
+  // input and output buffers of at least these sizes (outBytes 0: the call has no output).  The input gets 256 bytes more -- the decoders' 128-byte
+  // zero tail and their reads up to C + 64 live there --, the output 64.
+  bool reserve(uint64_t inBytes, uint64_t outBytes)
+  {
+    if (!grow(&D.monoIn, &D.monoInSize, inBytes + 256) || (outBytes && !grow(&D.monoOut, &D.monoOutSize, outBytes + 64)) || (!D.monoAux && hipMalloc(&D.monoAux, 256) != hipSuccess))
+      return false;
+    in = (uint8_t *)D.monoIn; out = (uint8_t *)D.monoOut; status = (uint32_t *)((uint8_t *)D.monoAux + 64);
+    return true;
+  }
+  bool reserve_ws(uint64_t bytes, WsKind kind = kCodecWs)
+  {
+    void **p = kind == kMonoWs ? &D.monoWs : &D.ws;
+    uint64_t *have = kind == kMonoWs ? &D.monoWsSize : &D.wsSize;
+    if (!grow(p, have, bytes))
+      return false;
+    ws = (uint8_t *)*p; wsSize = *have;
+    return true;
+  }
+  // n host bytes to in + at, zeroTail zero bytes behind them
+  bool up(const void *p, uint64_t n, uint64_t at = 0, uint32_t zeroTail = 0)
+  {
+    return (n == 0 || hipMemcpy(in + at, p, n, hipMemcpyHostToDevice) == hipSuccess) && (zeroTail == 0 || hipMemset(in + at + n, 0, zeroTail) == hipSuccess);
+  }
+  bool words(uint32_t *to, const void *dFrom, uint32_t count) { return hipMemcpy(to, dFrom, 4ull * count, hipMemcpyDeviceToHost) == hipSuccess; }
+  bool down(void *to, const void *dFrom, uint64_t n) { return hipMemcpy(to, dFrom, n, hipMemcpyDeviceToHost) == hipSuccess; }
+};
+
+} // namespace hsrle

@@ -121,7 +121,7 @@ constexpr uint32_t cut_long(const CodecInfo &c)
 // the codecs whose encoder state at a cut is fixed by the cut itself (no list, or a one-symbol list = the cut's symbol): plain / Packed / Short without or with a
 // one-symbol list, of 1 .. 8 byte symbols -- the chunks of their monolithic streams go to the windowed position-parallel encoders
 constexpr bool chunk_mode(const CodecInfo &c) { return (c.fam == PLAIN || c.fam == PACKED || c.fam == SHORT0 || c.fam == SHORT1) && c.S <= 8 && !c.greedy; }
-// windowed encoders, blocks of ANY size: plain / Packed of 1 .. 8 byte symbols write 8 or 32 bit fields whatever the block size (hsrle_capi_encode.inc: ppw_applies)
+// windowed encoders, blocks of ANY size: plain / Packed of 1 .. 8 byte symbols write 8 or 32 bit fields whatever the block size (hsrle_capi_container.h: ppw_applies)
 constexpr bool any_block_windowed(const CodecInfo &c) { return (c.fam == PLAIN || c.fam == PACKED) && c.S <= 8; }
 // Greedy with a list of ONE symbol: behind a stored run the list is that run's symbol, so a chunk's first guess is right (split_encode_applies)
 constexpr bool greedy_one_symbol_list(const CodecInfo &c) { return c.greedy && c.fam == SHORT1; }

@@ -1,7 +1,8 @@
 """The host side plans what it planned before the codec traits table (csrc/hsrle_codecs.h) replaced the codec-id arithmetic: tools/dump_host_plans.py over
 the current build against tests/golden/host_plans.json, which the same tool wrote from the build of the commit before -- encode path, container / monolithic
 encode and decode workspaces, index size and index workspace, for all 110 codecs over a grid of sizes, block sizes, compressed sizes and record spacings.
-No device is touched."""
+The "codec_free" rows do the same for the workspaces that take no codec id (low-entropy encode and decode, rle8m encode over four section counts); they
+were written from the build before the three hand-rolled scan-level layouts became one.  No device is touched."""
 import json
 import os
 import sys
@@ -29,3 +30,15 @@ def test_host_plans_are_the_recorded_ones():
         assert len(per_codec) == 110
         for name, values in per_codec.items():
             assert got[fn][name] == values, f"{fn}({name})"
+
+
+def test_codec_free_plans_are_the_recorded_ones():
+    import dump_host_plans
+
+    with open(GOLDEN) as f:
+        want = json.load(f)["codec_free"]
+    got = dump_host_plans.dump_codec_free(dump_host_plans.load())
+    assert sorted(got) == sorted(want)
+    assert len(want["hsrle_rle8m_compress_workspace_size"]) == len(dump_host_plans.SIZES32) * len(want["sections"])
+    for fn, values in want.items():
+        assert got[fn] == values, fn

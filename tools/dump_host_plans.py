@@ -4,6 +4,8 @@
   python tools/dump_host_plans.py [out.json]        (HSRLE_LIB=<path> picks another build of the library)
 
 tests/golden/host_plans.json is this tool's output for the build the codec traits table (csrc/hsrle_codecs.h) replaced;
+its "codec_free" rows (the low-entropy and rle8m workspaces, which take no codec id) were written from the build before
+csrc/hsrle_capi.hip was cut into its csrc/hsrle_capi_*.h parts and the three scan-level layouts became one.
 tests/test_host_plans.py asserts that the current build reproduces it value for value.  None of the calls below touches a device.
 hsrle_mono_tuning() is never called: the plans are those of the defaults.
 """
@@ -19,6 +21,7 @@ SIZES32 = [4096, (1 << 20) + 128, 88473600, 1 << 30]
 SIZES64 = SIZES32 + [8 << 30]
 BLOCKS = [128, 1024, 4096, 4224, 8192, 65536, 1 << 20]
 SPACINGS = [0, 512, 4096]
+SECTIONS = [1, 7, 4096, 262144]
 
 
 def compressed_sizes(U):
@@ -35,6 +38,9 @@ def load(path=LIB):
     for name, args in (("hsrle_compress_workspace_size_codec", [ci, u64, u32]), ("hsrle_compress_mono_workspace_size", [ci, u32]),
                        ("hsrle_decompress_mono_workspace_size", [ci, u32, u32]), ("hsrle_mono_index_size", [ci, u32, u32, u32]),
                        ("hsrle_mono_index_workspace_size", [ci, u32, u32, u32])):
+        getattr(L, name).restype = u64
+        getattr(L, name).argtypes = args
+    for name, args in (("hsrle_low_entropy_workspace_size", [u32]), ("hsrle_low_entropy_decompress_workspace_size", [u64]), ("hsrle_rle8m_compress_workspace_size", [u32, u32])):
         getattr(L, name).restype = u64
         getattr(L, name).argtypes = args
     return L
@@ -65,7 +71,17 @@ def dump(L):
                 vectors.append(v)
             which[nm] = vectors.index(v)
         out[fn] = {"vectors": vectors, "codec": which}
-    return {"grid": {"sizes32": SIZES32, "sizes64": SIZES64, "blocks": BLOCKS, "compressed": ["U/8", "U"], "spacings": SPACINGS}, "results": out}
+    return {"grid": {"sizes32": SIZES32, "sizes64": SIZES64, "blocks": BLOCKS, "compressed": ["U/8", "U"], "spacings": SPACINGS}, "results": out, "codec_free": dump_codec_free(L)}
+
+
+def dump_codec_free(L):
+    """the plans that take no codec id, over SIZES32 (rle8m: x SECTIONS, sizes outermost)"""
+    return {
+        "sections": SECTIONS,
+        "hsrle_low_entropy_workspace_size": [L.hsrle_low_entropy_workspace_size(U) for U in SIZES32],
+        "hsrle_low_entropy_decompress_workspace_size": [L.hsrle_low_entropy_decompress_workspace_size(U) for U in SIZES32],
+        "hsrle_rle8m_compress_workspace_size": [L.hsrle_rle8m_compress_workspace_size(U, n) for U in SIZES32 for n in SECTIONS],
+    }
 
 
 def expand(results):
@@ -77,7 +93,8 @@ if __name__ == "__main__":
     d = dump(load())
     # one line per entry point and part: short enough to read, few enough lines to review
     rows = ['  "%s": {"vectors": %s,\n    "codec": %s}' % (fn, json.dumps(r["vectors"], separators=(",", ":")), json.dumps(r["codec"], separators=(",", ":"))) for fn, r in d["results"].items()]
-    text = '{"grid": %s,\n "results": {\n%s\n }}' % (json.dumps(d["grid"]), ",\n".join(rows))
+    free = ",\n".join('  "%s": %s' % (k, json.dumps(v, separators=(",", ":"))) for k, v in d["codec_free"].items())
+    text = '{"grid": %s,\n "results": {\n%s\n },\n "codec_free": {\n%s\n }}' % (json.dumps(d["grid"]), ",\n".join(rows), free)
     if len(sys.argv) > 1:
         with open(sys.argv[1], "w") as f:
             f.write(text + "\n")
