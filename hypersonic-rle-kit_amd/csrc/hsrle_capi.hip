@@ -109,6 +109,12 @@ int hsrle_encode_path(int codec, uint64_t uncompressedSize, uint32_t blockSize)
   return HSRLE_PATH_RING;
 }
 
+int hsrle_decode_ring(int codec, uint64_t uncompressedSize, uint64_t payloadSize)
+{
+  if (codec < 0 || codec >= kCodecCount) return -1;
+  return decode_ring_small(kCodecs[codec], uncompressedSize, payloadSize + HSRLE_CONTAINER_TAIL_PAD) ? 64 : 128;   // (what DecodeArgs::payloadEnd - payload is for this container)
+}
+
 #ifndef HSRLE_BUILD_ID
 #define HSRLE_BUILD_ID "unknown"
 #endif

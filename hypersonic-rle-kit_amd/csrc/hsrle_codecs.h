@@ -128,5 +128,12 @@ constexpr bool greedy_one_symbol_list(const CodecInfo &c) { return c.greedy && c
 // the codecs that have a many-lane chunk encoder but no run list encoder: small containers of 1 .. 4 KiB blocks take the split encode IF the
 // caller's workspace has its regions (hsrle_compress_workspace_size_codec; the library's own scratch always has)
 constexpr bool split_small(const CodecInfo &c) { return is_single(c) || c.S == 16 || greedy_one_symbol_list(c); }
+// Plain block decode: the ratio (payload + tail pad) / uncompressed size, in thousandths, below which a container takes the decoder instantiation with the
+// 64-byte stream ring (hsrle_launch.h: decode_ring_small says why and when); 0 = the codec has no such instantiation.  THE statement of these thresholds.
+// 1 / 2 byte symbols: 250 -- rle16_sym at 0.23 still gains 6 %.  3 / 4 byte symbols: 215 (round 4; 200 before: rle32_3symlut_sym video-shaped at 0.2042 gains
+// 9 % with the small ring) -- 8 GiB video-shaped rle32_3symlut_byte (0.17) +16 %, rle24_7symlut_byte_short (0.19) +12 %, every 24 / 32 bit row of the sweep
+// below 0.2 gains 10 - 20 %, but rle24_sym (0.26) -3 %, rle32_sym (0.30) -8 %.  6 / 8 / 16 byte symbols: never (their packets are large: below a ratio of 0.2
+// the 64-byte ring cost the 7-symbol LUT codecs 24 % on run-distributed data, 19 % on video-shaped; sweep of 8 GiB buffers).
+constexpr uint32_t small_ring_per_mille(const CodecInfo &c) { return c.S <= 2 ? 250u : (c.S <= 4 ? 215u : 0u); }
 
 } // namespace hsrle

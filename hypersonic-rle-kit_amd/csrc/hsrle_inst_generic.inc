@@ -22,19 +22,20 @@ namespace hsrle {
 // 2 byte symbols: the decoder's stream ring is chosen by the container's ratio (launch_decode_ring, hsrle_launch.h)
 #if HSRLE_S == 2
 #define HSRLE_DECODE_LAUNCH(FAM, AL) (windowed(a) ? launch_decode(k_decode_blocks<FAM, 2, AL, kDecodeTile, kDecodeRing, kDecodeStep, true, true, true>, a, st) : (a.entries ? launch_decode(k_decode_blocks<FAM, 2, AL, kDecodeTile, kDecodeRing, kDecodeStep>, a, st) \
-                                                : launch_decode_ring(k_decode_blocks<FAM, 2, AL, kDecodeTile, kDecodeRing, kDecodeStep, true, false>, \
-                                                                     k_decode_blocks<FAM, 2, AL, kDecodeTile, 64, kDecodeStep, true, false>, a, st)))
+                                                : launch_decode_ring<codec_id(FAM, 2, AL)>(k_decode_blocks<FAM, 2, AL, kDecodeTile, kDecodeRing, kDecodeStep, true, false>, \
+                                                                                            k_decode_blocks<FAM, 2, AL, kDecodeTile, 64, kDecodeStep, true, false>, a, st)))
 #elif HSRLE_S >= 6 && !defined(HSRLE_DECODE_ALWAYS_ENT)
 // 6 / 8 byte symbols: no small ring (their packets are large: below a ratio of 0.2 the 64-byte ring cost the 7-symbol LUT codecs 24 % on
 // run-distributed data, 19 % on video-shaped; sweep of 8 GiB buffers); plain containers take the instantiation without the record prologue
+static_assert(small_ring_per_mille(kCodecs[codec_id(PLAIN, HSRLE_S, 1)]) == 0u, "the codec rows (hsrle_codecs.h) give this width a 64-byte ring: instantiate it");
 #define HSRLE_DECODE_LAUNCH(FAM, AL) (windowed(a) ? launch_decode(k_decode_blocks<FAM, HSRLE_S, AL, kDecodeTile, kDecodeRing, kDecodeStep, true, true, true>, a, st) : (a.entries ? launch_decode(k_decode_blocks<FAM, HSRLE_S, AL, kDecodeTile, kDecodeRing, kDecodeStep>, a, st) \
                                                 : launch_decode(k_decode_blocks<FAM, HSRLE_S, AL, kDecodeTile, kDecodeRing, kDecodeStep, true, false>, a, st)))
 #elif HSRLE_S >= 3 && !defined(HSRLE_DECODE_ALWAYS_ENT)
 // plain containers take the instantiation without the entry-record prologue (hsrle_decode.hip.h: ENT; same-box A/B on run-distributed
 // data: rle32_3symlut_byte +6 %, rle48_7symlut_sym +4 %, rle64_sym +-0; the 128 bit codecs +10 %)
 #define HSRLE_DECODE_LAUNCH(FAM, AL) (windowed(a) ? launch_decode(k_decode_blocks<FAM, HSRLE_S, AL, kDecodeTile, kDecodeRing, kDecodeStep, true, true, true>, a, st) : (a.entries ? launch_decode(k_decode_blocks<FAM, HSRLE_S, AL, kDecodeTile, kDecodeRing, kDecodeStep>, a, st) \
-                                                : launch_decode_ring<215>(k_decode_blocks<FAM, HSRLE_S, AL, kDecodeTile, kDecodeRing, kDecodeStep, true, false>, \
-                                                                          k_decode_blocks<FAM, HSRLE_S, AL, kDecodeTile, 64, kDecodeStep, true, false>, a, st)))
+                                                : launch_decode_ring<codec_id(FAM, HSRLE_S, AL)>(k_decode_blocks<FAM, HSRLE_S, AL, kDecodeTile, kDecodeRing, kDecodeStep, true, false>, \
+                                                                                                  k_decode_blocks<FAM, HSRLE_S, AL, kDecodeTile, 64, kDecodeStep, true, false>, a, st)))
 #else
 #define HSRLE_DECODE_LAUNCH(FAM, AL) (windowed(a) ? launch_decode(k_decode_blocks<FAM, HSRLE_S, AL, kDecodeTile, kDecodeRing, kDecodeStep, true, true, true>, a, st) : launch_decode(k_decode_blocks<FAM, HSRLE_S, AL, kDecodeTile, kDecodeRing, kDecodeStep>, a, st))
 #endif

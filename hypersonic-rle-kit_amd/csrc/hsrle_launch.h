@@ -178,17 +178,23 @@ inline hipError_t launch_decode(KERNEL k, const DecodeArgs &a, hipStream_t st)
 // stream ring (12 instead of 9 waves per CU; a lane rarely needs more than 64 stream bytes for 128 output bytes there, and one that
 // does finishes in the second pass).  8 GiB video-shaped rle8_packed (ratio 0.18): 3.90 -> 3.34 ms; at ratio 0.43 it would lose 9 %,
 // on run-distributed data 9 - 25 %.  Blocks decoded from entry records (monolithic streams, split decode) keep the 128-byte ring.
-// HSRLE_DEC_RING=64 / 128 in the environment forces one (tests, A/B).
-// (PER_MILLE: the ratio below which the small ring is taken.  1 / 2 byte symbols: 250 -- rle16_sym at 0.23 still gains 6 %; wider symbols:
-//  3 / 4 byte symbols: 215 (round 4; 200 before: rle32_3symlut_sym video-shaped at 0.2042 gains 9 % with the small ring) -- 8 GiB video-shaped rle32_3symlut_byte (0.17) +16 %, rle24_7symlut_byte_short (0.19) +12 %, every 24 / 32 bit
-//  row of the sweep below 0.2 gains 10 - 20 %, but rle24_sym (0.26) -3 %, rle32_sym (0.30) -8 %.  6 / 8 byte symbols: never)
-template <int PER_MILLE = 250, typename K128, typename K64>
-inline hipError_t launch_decode_ring(K128 k128, K64 k64, const DecodeArgs &a, hipStream_t st)
+// HSRLE_DEC_RING=64 / 128 in the environment forces one (tests, A/B; experiment builds).
+// THE predicate: launch_decode_ring below and hsrle_decode_ring (include/hsrle.h) both ask it, with the codec's threshold from its row (hsrle_codecs.h:
+// small_ring_per_mille; a codec without a 64-byte instantiation never takes one, forced or not).  readableBytes = payloadSize + the tail pad.
+inline bool decode_ring_small(const CodecInfo &c, uint64_t U, uint64_t readableBytes)
 {
   static const int forced = (int)knob_u32("HSRLE_DEC_RING", 0);
-  const uint64_t payloadBytes = (uint64_t)(a.payloadEnd - a.payload);
-  const bool small = forced ? forced == 64 : (a.entries == nullptr && a.residentWorkgroups == nullptr && payloadBytes * 1000u < a.U * (uint64_t)PER_MILLE);
-  if (small && a.entries == nullptr) return launch_decode(k64, a, st);
+  const uint64_t perMille = small_ring_per_mille(c);
+  if (perMille == 0u) return false;
+  return forced ? forced == 64 : readableBytes * 1000u < U * perMille;
+}
+// CODEC: the id of a codec this decoder serves (ids that share a decoder share the symbol width, and with it the threshold).  A query
+// (a.residentWorkgroups) has U == 0 and gets the 128-byte instantiation unless one is forced.
+template <int CODEC, typename K128, typename K64>
+inline hipError_t launch_decode_ring(K128 k128, K64 k64, const DecodeArgs &a, hipStream_t st)
+{
+  static_assert(small_ring_per_mille(kCodecs[CODEC]) != 0u, "a 64-byte ring instantiation for a codec whose row says it never takes one");
+  if (a.entries == nullptr && decode_ring_small(kCodecs[CODEC], a.U, (uint64_t)(a.payloadEnd - a.payload))) return launch_decode(k64, a, st);
   return launch_decode(k128, a, st);
 }
 

@@ -7,6 +7,7 @@
 
 namespace hsrle {
 
+static_assert(small_ring_per_mille(kCodecs[codec_id(PLAIN, 16, 1)]) == 0u, "the codec rows (hsrle_codecs.h) give this width a 64-byte ring: instantiate it");
 static hipError_t dec_sym(const DecodeArgs &a, hipStream_t st) { return windowed(a) ? launch_decode(k_decode_blocks<PLAIN, 16, 1, kDecodeTile, kDecodeRing, kDecodeStep, true, true, true>, a, st) : a.entries ? launch_decode(k_decode_blocks<PLAIN, 16, 1, kDecodeTile, kDecodeRing, kDecodeStep>, a, st) : launch_decode(k_decode_blocks<PLAIN, 16, 1, kDecodeTile, kDecodeRing, kDecodeStep, true, false>, a, st); }
 static hipError_t dec_sym_packed(const DecodeArgs &a, hipStream_t st) { return windowed(a) ? launch_decode(k_decode_blocks<PACKED, 16, 1, kDecodeTile, kDecodeRing, kDecodeStep, true, true, true>, a, st) : a.entries ? launch_decode(k_decode_blocks<PACKED, 16, 1, kDecodeTile, kDecodeRing, kDecodeStep>, a, st) : launch_decode(k_decode_blocks<PACKED, 16, 1, kDecodeTile, kDecodeRing, kDecodeStep, true, false>, a, st); }
 static hipError_t dec_byte(const DecodeArgs &a, hipStream_t st) { return windowed(a) ? launch_decode(k_decode_blocks<PLAIN, 16, 0, kDecodeTile, kDecodeRing, kDecodeStep, true, true, true>, a, st) : a.entries ? launch_decode(k_decode_blocks<PLAIN, 16, 0, kDecodeTile, kDecodeRing, kDecodeStep>, a, st) : launch_decode(k_decode_blocks<PLAIN, 16, 0, kDecodeTile, kDecodeRing, kDecodeStep, true, false>, a, st); }

@@ -88,6 +88,8 @@ def _lib():
     L.hsrle_experiments_enabled.restype = ci
     L.hsrle_encode_path.restype = ci
     L.hsrle_encode_path.argtypes = [ci, ctypes.c_uint64, ctypes.c_uint32]
+    L.hsrle_decode_ring.restype = ci
+    L.hsrle_decode_ring.argtypes = [ci, ctypes.c_uint64, ctypes.c_uint64]
     L.hsrle_build_id.restype = ctypes.c_char_p
     L.hsrle_suggest_block_size.restype = u32
     L.hsrle_suggest_block_size.argtypes = [u64]
@@ -221,6 +223,17 @@ def encode_path(codec, size, block_size):
     r = int(_lib().hsrle_encode_path(cid, size, block_size))
     if r < 0:
         raise ValueError("hsrle_encode_path: bad codec, size or block size")
+    return r
+
+
+def decode_ring(codec, usize, payload_size):
+    """Which stream ring (64 or 128 bytes per lane) the plain block decode (`decompress_async`, block ranges included) takes for a container of `codec`
+    with these header fields (include/hsrle.h: hsrle_decode_ring; needs no device).  Split decode by records and range decode always use 128; `decompress`
+    takes the split decode for containers of fewer than 131 072 blocks and is not what this reports."""
+    cid = codec if isinstance(codec, int) else codec_id(codec)
+    r = int(_lib().hsrle_decode_ring(cid, usize, payload_size))
+    if r < 0:
+        raise ValueError("hsrle_decode_ring: bad codec")
     return r
 
 

@@ -507,6 +507,15 @@ int hsrle_experiments_enabled(void);
  * position-parallel Short codecs with blocks below 1 MiB: 86 codecs (not: the 8 bit Single codecs, the 128 bit codecs) */
 int hsrle_encode_path(int codec, uint64_t uncompressedSize, uint32_t blockSize);
 
+/* Which stream ring (bytes per lane in LDS: 64 or 128) the block decoder of hsrle_decompress_dev_async / hsrle_decompress_blocks_dev_async takes for a
+ * container of this codec with these header fields (no device needed; the output is the same bytes whichever it is -- this is for reading profiles and
+ * for tests that must know which kernel they ran).  Containers whose streams shrink far enough take the instantiation with the small ring: 1 .. 4 byte
+ * symbols only, the threshold goes by the symbol width (csrc/hsrle_codecs.h: small_ring_per_mille).  A block range of a container takes what the whole
+ * container takes.  Launches from entry records (split decode by sub-blocks, monolithic streams) and with an output window
+ * (hsrle_decompress_range_dev_async) always use 128 and are not what this reports; nor is hsrle_decompress_dev, which takes the split decode (no ring, or 128) for
+ * every container of fewer than 131 072 blocks and this kernel only above.  -1: bad codec. */
+int hsrle_decode_ring(int codec, uint64_t uncompressedSize, uint64_t payloadSize);
+
 /* A hash of the library's sources and build flags (set by the Makefile; "unknown" for other build recipes): measurement files that
  * describe one build of the kernels (profiles/r03_traffic.json) carry it, and bench.py refuses a file of another build. */
 const char *hsrle_build_id(void);

@@ -1067,8 +1067,11 @@ static void out_copy(dst_t *o, src_t *s, uint64_t k)
   o->at += k;
 }
 
+static uint64_t g_run_packets;   /* run expansions since hso_run_packets reset it: every decoder below expands one run per packet */
+
 static void out_fill(dst_t *o, const uint8_t *sym, uint32_t S, uint64_t k)
 {
+  g_run_packets++;
   if (o->at + k > o->cap) { o->bad = 1; return; }
   uint8_t *q = o->o + o->at;
   if (S == 1)
@@ -1911,4 +1914,16 @@ uint64_t hso_hash_blocks(int family, int S, int aligned, const uint8_t *pIn, uin
 void hso_rollups(const uint64_t *hashes, uint64_t n, uint64_t group, uint64_t *out)
 {
   for (uint64_t g = 0; g * group < n; g++) out[g] = hsrle_rollup(hashes + g * group, (n - g * group) < group ? (n - g * group) : group);
+}
+
+/* packets of a stream that carry a run (the terminator is not one): decodes it into a scratch buffer and counts; 0 if it does not decode to outSize bytes.
+ * Test infrastructure (how dense a fixture block's packet chain is); not reentrant. */
+uint64_t hso_run_packets(int family, int S, int aligned, const uint8_t *pIn, uint32_t inSize, uint32_t outSize)
+{
+  uint8_t *tmp = (uint8_t *)malloc((size_t)outSize + 1);
+  if (!tmp) return 0;
+  g_run_packets = 0;
+  const uint32_t got = hso_decompress(family, S, aligned, pIn, inSize, tmp, outSize);
+  free(tmp);
+  return got == outSize ? g_run_packets : 0;
 }

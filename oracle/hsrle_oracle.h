@@ -74,6 +74,8 @@ uint32_t hso_compress_blocks(int family, int symbolBytes, int symAligned,
                              uint8_t *pOut, uint32_t stride, uint32_t *pSizes);
 
 /* Decode nBlocks block streams (payload + offsets[i] .. offsets[i+1]) into pOut + i * blockSize; returns bytes produced. */
+/* run-carrying packets of one stream (test infrastructure: how dense a fixture's packet chain is); 0 if the stream does not decode to outSize bytes */
+uint64_t hso_run_packets(int family, int symbolBytes, int symAligned, const uint8_t *pIn, uint32_t inSize, uint32_t outSize);
 uint64_t hso_decompress_blocks(int family, int symbolBytes, int symAligned, const uint8_t *payload, const uint64_t *offsets,
                                uint64_t nBlocks, uint32_t blockSize, uint8_t *pOut, uint64_t outSize);
 

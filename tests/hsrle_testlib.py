@@ -186,6 +186,13 @@ class Oracle:
         size = self.lib.hso_decompress(codec.family, codec.S, codec.aligned, stream, len(stream), out, out_size)
         return out.raw[:size] if size else None
 
+    def run_packets(self, codec, stream, out_size):
+        """How many packets of `stream` carry a run (the terminator is not one); 0 if it does not decode to out_size bytes."""
+        self.lib.hso_run_packets.restype = ctypes.c_uint64
+        self.lib.hso_run_packets.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32]
+        stream = bytes(stream)
+        return int(self.lib.hso_run_packets(codec.family, codec.S, codec.aligned, stream, len(stream), out_size))
+
     def call(self, name, data, out_cap):
         data = bytes(data)
         out = ctypes.create_string_buffer(max(out_cap, 1))

@@ -140,6 +140,33 @@ def test_encode_path_selection(lib):
     assert lib.hsrle_encode_path(-1, frame, 4096) == -1 and lib.hsrle_encode_path(0, frame, 1000) == -1 and lib.hsrle_encode_path(0, 0, 4096) == -1
 
 
+def test_decode_ring_rule(lib):
+    """hsrle_decode_ring (no device): the stream ring of the plain block decode.  The rule, stated here independently of csrc/hsrle_codecs.h: the
+    64-byte ring iff (payloadSize + 32) * 1000 < uncompressedSize * T with T = 250 for 1 / 2 byte symbols and 215 for 3 / 4 byte symbols; 6, 8 and
+    16 byte symbols take 128 at any ratio.  Every codec id, the last payload size on the small side and the first on the other, at a size whose
+    products need 64 bits too."""
+    from hsrle_testlib import CODECS
+
+    lib.hsrle_decode_ring.restype = ctypes.c_int
+    lib.hsrle_decode_ring.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64]
+    lib.hsrle_experiments_enabled.restype = ctypes.c_int
+    assert not lib.hsrle_experiments_enabled() or not os.environ.get("HSRLE_DEC_RING"), "an experiments build with a forced ring does not follow the rule"
+    for cid, c in enumerate(CODECS):
+        T = 250 if c.S <= 2 else 215 if c.S <= 4 else 0
+        for U in (4096, 1000000, 786432 + 2053, (8 << 30) + 12345, 1 << 44):
+            if T == 0:
+                for payload in (0, 1, U // 8, U // 4, U, 2 * U):
+                    assert lib.hsrle_decode_ring(cid, U, payload) == 128, (c.key, U, payload)
+                continue
+            edge = -(-U * T // 1000)                 # smallest payload + 32 that is NOT below the threshold: ceil(U * T / 1000)
+            assert (edge - 1) * 1000 < U * T <= edge * 1000
+            assert lib.hsrle_decode_ring(cid, U, edge - 32 - 1) == 64, (c.key, U)
+            assert lib.hsrle_decode_ring(cid, U, edge - 32) == 128, (c.key, U)
+            assert lib.hsrle_decode_ring(cid, U, 0) == 64 and lib.hsrle_decode_ring(cid, U, U) == 128, (c.key, U)
+    assert lib.hsrle_decode_ring(-1, 4096, 10) == -1 and lib.hsrle_decode_ring(110, 4096, 10) == -1
+    assert lib.hsrle_decode_ring(0, 0, 0) == 128      # (no such container; nothing is below a threshold of 0 bytes)
+
+
 def test_codec_table_matches_tests_table(lib):
     from hsrle_testlib import CODECS
 

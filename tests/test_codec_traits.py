@@ -21,8 +21,8 @@ int main()
   for (int c = 0; c < kCodecCount; c++)
   {
     const CodecInfo &i = kCodecs[c];
-    printf("%%d %%s %%d %%d %%d %%d %%d %%d %%u %%u %%d\n", c, i.name, (int)i.fam, (int)i.S, (int)i.aligned, (int)i.greedy, list_len(i), state_slots(i), header_size(i), cut_long(i),
-           codec_id(i.fam, i.S, i.aligned, i.greedy));
+    printf("%%d %%s %%d %%d %%d %%d %%d %%d %%u %%u %%d %%u\n", c, i.name, (int)i.fam, (int)i.S, (int)i.aligned, (int)i.greedy, list_len(i), state_slots(i), header_size(i), cut_long(i),
+           codec_id(i.fam, i.S, i.aligned, i.greedy), small_ring_per_mille(i));
   }
   return 0;
 }
@@ -40,7 +40,7 @@ def rows(tmp_path_factory):
     src.write_text(PROGRAM % HEADER)
     subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", str(src), "-o", str(exe)])
     out = subprocess.check_output([str(exe)], text=True)
-    keys = ("id", "name", "fam", "S", "aligned", "greedy", "K", "slots", "header", "cut", "found")
+    keys = ("id", "name", "fam", "S", "aligned", "greedy", "K", "slots", "header", "cut", "found", "ring")
     return [{k: (v if k == "name" else int(v)) for k, v in zip(keys, line.split())} for line in out.splitlines()]
 
 
@@ -74,3 +74,9 @@ def test_header_size(rows):
 
 def test_every_codec_has_a_cut_length(rows):
     assert all(r["cut"] > r["S"] for r in rows)
+
+
+def test_small_ring_threshold_goes_by_the_symbol_width(rows):
+    """The decoder's 64-byte stream ring: below a quarter for 1 / 2 byte symbols, below 0.215 for 3 / 4 byte symbols, never for wider ones."""
+    for r in rows:
+        assert r["ring"] == (250 if r["S"] <= 2 else 215 if r["S"] <= 4 else 0), r["name"]
