@@ -317,6 +317,10 @@ int hsrle_mono_decompress_range_dev_async(const void *dStream, const void *dInde
  *   [48] uint8_t  reserved[16]
  *   [64] uint64_t offset[blockCount + 1]   (relative to the payload start; offset[blockCount] == payloadSize)
  *   [64 + 8 * (blockCount + 1)] payload: block streams back to back, each a complete reference stream
+ *       (any stream the reference's decoder of the codec accepts -- whatever encoder wrote it -- with ONE exception: a packet that produces no byte, i.e. no literal
+ *       and a run of zero bytes, which only the sym-aligned Packed codecs of 3 .. 16 byte symbols and the sym-aligned list codecs of wider symbols can express and no
+ *       encoder of the kit writes.  Every decoder here -- block, split, windowed, monolithic, drop-in -- refuses such a stream as malformed and writes nothing
+ *       outside its output)
  *   32 zero bytes (lets the decoder use 16-byte vector loads up to the last stream byte)
  */
 #define HSRLE_CONTAINER_HEADER_SIZE 64u
