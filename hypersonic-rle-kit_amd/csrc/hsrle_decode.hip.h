@@ -388,10 +388,10 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
 
   // ---- ring top-up.  issue(): LPR loads; in load q, lanes LPR*g .. LPR*g+LPR-1 read Q contiguous bytes of row RPL*q+g ----
   u32x4 pf[LPR];
-  uint32_t pfPos[LPR];                                              // stream position of the chunk held in / on its way to pf[q] (~0: none)
+  uint32_t pfPos[LPR];                                              // stream position of the chunk held in / on its way to pf[q] (~0, or at / behind lim: none)
 #pragma unroll
   for (int q = 0; q < LPR; q++) { pf[q] = u32x4{ 0, 0, 0, 0 }; pfPos[q] = 0xFFFFFFFFu; }
-  uint64_t myBase[LPR];                                             // stream starts of the LPR rows this lane helps to load
+  const uint8_t *pfPtr[LPR];                                        // its address: the stream start of row q * RPL + lane / LPR (one of the LPR rows this lane helps to load) + pfPos[q]
   // whether a stream has a chunk left for a lane: from the row's lim kept in a register per served row, or -- where registers are
   // what stands between 8 and 9 waves per CU (the LUT decoders of the wide symbols) -- from a 4-bit count the owner packs below E
   constexpr bool kPackLim = TR::kMtf && TR::K > 1 && S > 1;
@@ -438,6 +438,7 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
 #endif
   static_assert(RPL % 8 == 0, "the ring swizzle of row q * RPL + g must not depend on q");
   const uint32_t serveBase = ((lane / LPR) * (uint32_t)RS) ^ rsw_of(lane / LPR);   // ring row (swizzled) of the first row this lane serves
+  [[maybe_unused]] const uint32_t serveAt = serveBase ^ (((lane % LPR) * 16u) & RMASK);   // Q % R == 0: the slot of every chunk this lane lands
   auto topup = [&]() {
 #ifdef HSRLE_STAMPS
     tq0 = __builtin_readcyclecounter();
@@ -447,32 +448,37 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
     HS_EXCHANGE(ri, kPackLim ? (E | umin(15u, (lim - E) >> 4)) : E, LPR)      // E is a multiple of 16
     wave_sync();
     HS_XSTAMP(tx0)
+    // The ring writes first, then the requests, each one predicate region per chunk register (a request in front of a later register's ring write would put
+    // a fresh load in front of that write's wait).  pfPos[q] stays (lane % LPR) * 16 modulo Q, so where the ring divides Q the ring slot is the lane's own
+    // for good; pfPtr[q] runs along with pfPos[q], so no address is rebuilt from the row's base; a lane whose part of the stream is complete needs no mark:
+    // its pfPos[q] then lies at or behind lim, which no E exceeds.
     bool landed[LPR];
 #pragma unroll
     for (int q = 0; q < LPR; q++)
     {
-      landed[q] = pfPos[q] < (ri[q] & ~15u);
+      landed[q] = pfPos[q] < (kPackLim ? (ri[q] & ~15u) : ri[q]);       // (not packed: E is a multiple of 16 as it is)
       if (landed[q])                                                    // row q * RPL + lane / LPR: the q term is the instruction's offset field
-        lds_st128(ring + ((serveBase ^ (pfPos[q] & RMASK)) + (uint32_t)q * RPL * RS), pf[q]);
+        lds_st128(ring + (((uint32_t)Q % (uint32_t)R == 0u ? serveAt : (serveBase ^ (pfPos[q] & RMASK))) + (uint32_t)q * RPL * RS), pf[q]);
     }
     HS_XSTAMP(tx1)
 #pragma unroll
     for (int q = 0; q < LPR; q++)
     {
-#ifdef HSRLE_REQ_STATS
-      count_requests(landed[q] && (kPackLim ? (((pfPos[q] + (uint32_t)Q - (ri[q] & ~15u)) >> 4) < (ri[q] & 15u)) : (limq[q] - pfPos[q] > (uint32_t)Q)));
-#endif
+      // the chunk Q bytes further on exists iff it starts below lim (no wrap: a landed chunk starts below lim <= 0xFFFFFF80)
+      bool more = false;
       if (landed[q])
       {
-        // the chunk Q bytes further on exists iff it starts below lim
-        if (kPackLim ? (((pfPos[q] + (uint32_t)Q - (ri[q] & ~15u)) >> 4) < (ri[q] & 15u)) : (limq[q] - pfPos[q] > (uint32_t)Q))
+        pfPos[q] += (uint32_t)Q;
+        more = kPackLim ? (((pfPos[q] - (ri[q] & ~15u)) >> 4) < (ri[q] & 15u)) : (pfPos[q] < limq[q]);
+        if (more)
         {
-          pfPos[q] += (uint32_t)Q;
-          pf[q] = ld128(payload + myBase[q] + pfPos[q]);
+          pfPtr[q] += Q;
+          pf[q] = ld128(pfPtr[q]);
         }
-        else
-          pfPos[q] = 0xFFFFFFFFu;                                         // this lane's part of the stream is complete
       }
+#ifdef HSRLE_REQ_STATS
+      count_requests(more);
+#endif
     }
     HS_XSTAMP(tx2)
   };
@@ -483,7 +489,7 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
   {
     const int r = (int)((uint32_t)q * RPL + lane / LPR);
     const uint32_t lo32 = (uint32_t)__shfl((int)(uint32_t)myBase0, r, 64), hi32 = (uint32_t)__shfl((int)(uint32_t)(myBase0 >> 32), r, 64);
-    myBase[q] = ((uint64_t)hi32 << 32) | lo32;
+    pfPtr[q] = payload + (((uint64_t)hi32 << 32) | lo32);             // (+ pfPos[q] below)
   }
 #pragma unroll
   for (int q = 0; q < LPR; q++)
@@ -497,7 +503,8 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
 #ifdef HSRLE_REQ_STATS
     count_requests(pfPos[q] < rowLim);
 #endif
-    if (pfPos[q] < rowLim) pf[q] = ld128(payload + myBase[q] + pfPos[q]);
+    pfPtr[q] += pfPos[q];
+    if (pfPos[q] < rowLim) pf[q] = ld128(pfPtr[q]);
     else pfPos[q] = 0xFFFFFFFFu;
   }
   for (int k = 0; k < (R / Q > 0 ? R / Q : 1); k++)
@@ -597,6 +604,22 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
 #else
 #define HS_STAMP(acc)
 #endif
+
+  // full-row flush (at the flush below): the lane's loop-invariant tile address and output offset.  The offset is a 32-bit one beside a scalar row
+  // pointer, so launches whose 64 rows span 4 GiB or more (blocks go up to 1 GiB) keep to the general flush.
+#if defined(HSRLE_ABLATE_STORES) || defined(HSRLE_NO_FULL_ROW_FLUSH)   // (timing-only diagnostic builds / A/B builds: the general flush only)
+  constexpr bool kFullRowFlush = false;
+#else
+  constexpr bool kFullRowFlush = CAP == 0u && !WIN;
+#endif
+  [[maybe_unused]] const bool fullRowOK = (uint64_t)B * 64u <= 0xFFFFFFFFull;
+  [[maybe_unused]] const uint32_t fullRowT = fullRowOK ? (uint32_t)T : 0xFFFFFFFFu;   // what a lane must have produced behind the common base (never: no lane does)
+  [[maybe_unused]] const uint32_t fullTileAt = (lane / CPR) * (uint32_t)TS + (((lane % CPR) * 16u) ^ tsw_of(lane / CPR));   // tsw_of(q * RPI + r) == tsw_of(r)
+  [[maybe_unused]] uint32_t fullOutAt[CPR];                              // of chunk (lane % CPR) of row q * RPI + lane / CPR, relative to the wave's first row
+#pragma unroll
+  for (int q = 0; q < CPR; q++)
+    fullOutAt[q] = fullRowOK ? ((uint32_t)q * RPI + lane / CPR) * B + (lane % CPR) * 16u : 0u;
+  static_assert(RPI % 8 == 0, "the tile swizzle of row q * RPI + r must not depend on q");
 
   [[maybe_unused]] bool skippedFlush = false;                          // capped rounds: the last trip went round again without a flush
   while (__ballot(!done && o < blen) != 0ull)
@@ -796,7 +819,10 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
             run = lastNow ? 0u : (TR::kShort ? cnt + TR::SMINS - 2u : cnt + shortv - (TR::kLut ? 2u : 1u));
             if (lastNow) fl |= F_LAST;
             sp += used;
-            if (hbad || sp > slen || lit > slen - sp || (lit == 0u && run == 0u && !lastNow)) { err |= DEC_ERR_STREAM; fl |= F_DONE; }
+            // the stream check as mask arithmetic (no branch, no predicate region): a bad packet sets the error bit and F_DONE in this very trip
+            const bool bad = (hbad != 0u) | (sp > slen) | (lit > slen - sp) | (((lit | run) == 0u) & !lastNow);
+            err |= bad ? (uint32_t)DEC_ERR_STREAM : 0u;
+            fl |= bad ? F_DONE : 0u;
           }
         }
 
@@ -1358,6 +1384,41 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
       if (!skippedFlush && (uint32_t)__builtin_popcountll(__ballot(starved && !done)) >= HSRLE_DEC_STARVED_MIN) { skippedFlush = true; continue; }
       skippedFlush = false;
 #endif
+    }
+
+    // ---- full-row flush (uncapped rounds without an output window): block sizes are multiples of T, so in steady state every lane of the wave has
+    //      produced exactly T bytes behind one common base -- all but the rounds of a partial wave, of a lane that ended in an error and of the
+    //      buffer's last block.  One wave-uniform test then replaces the exchange of base | chunks and the per-store predicates and addresses of
+    //      the general flush below: the same chunks go to the same addresses in the same order, from the loop-invariant tile addresses, to
+    //      (scalar) row pointer of (q, first lane's row) + uniform base, plus a loop-invariant 32-bit lane offset ----
+    if constexpr (kFullRowFlush)
+    {
+      const uint32_t ubase = __builtin_amdgcn_readfirstlane(base);
+      if ((__builtin_amdgcn_ballot_w64(base == ubase) & __builtin_amdgcn_ballot_w64(o - fullRowT == ubase)) == ~0ull)
+      {
+        uint8_t *const waveOut = outw + ((uint64_t)wgFirst * B + ubase);
+#pragma unroll
+        for (int h = 0; h < CPR; h += FH)                                // (FH at a time: the general flush's order and register bound)
+        {
+          u32x4 fv[FH];
+#pragma unroll
+          for (int k = 0; k < FH; k++)
+            fv[k] = lds_ld128(tile + fullTileAt + (uint32_t)(h + k) * RPI * TS);
+#pragma unroll
+          for (int k = 0; k < FH; k++)
+          {
+            // (no instruction: keeps the zero extension beside the store, which then takes the scalar pointer + 32-bit offset form.  Correct with any code
+            //  generation, but the path's 40 instructions and the 8 VGPRs of the offsets are this compiler's: hoisted extensions come back as eight 64-bit
+            //  pairs (166 VGPRs in the headline kernel).  Run tools/decode_resources.py --against the committed table after every toolchain change.)
+            asm volatile("" : "+v"(fullOutAt[h + k]));
+            __builtin_nontemporal_store(fv[k], (u32x4_unaligned *)(waveOut + fullOutAt[h + k]));
+          }
+        }
+        base += (uint32_t)T;
+        wave_sync();
+        HS_STAMP(tFlush)
+        continue;
+      }
     }
 
     // ---- flush: whole 16-byte chunks only.  A row that ends inside a chunk (lane starved, or the block tail) keeps that

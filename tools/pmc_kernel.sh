@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/pmc_$tag; mkdir -p $O; cd $R
 for grp in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_WAVE_CYCLES" "SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS" "SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_ANY SQ_THREAD_CYCLES_VALU" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_BRANCH SQ_IFETCH"; do
   n=$(echo $grp | tr ' ' '_' | cut -c1-40)
-  timeout -k 5 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $O/$n -o p -- python3 "$@" > $O/$n.log 2>&1 || echo "pass failed: $grp"
+  timeout -k 5 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $O/$n -o p -- python3 "$@" > $O/$n.log 2>&1 || { echo "pass failed: $grp (no further pass is started)"; failed=1; break; }
 done
 python3 - <<PY > $O/summary.txt
 import csv, glob, collections
@@ -19,3 +19,4 @@ for c, v in sorted(vals.items()):
     print(c, "avg per launch", sum(v) / len(v), "launches", len(v))
 PY
 cat $O/summary.txt
+exit ${failed:-0}

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/traffic_$tag; mkdir -p $O; cd $R
 for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum" "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum"; do
   n=$(echo $grp | tr ' ' '_' | cut -c1-30)
-  timeout -k 5 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $O/pmc_$n -o p -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu --no-extras > $O/pmc_$n.log 2> $O/pmc_$n.err || echo "pass failed: $grp"
+  timeout -k 5 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $O/pmc_$n -o p -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu --no-extras > $O/pmc_$n.log 2> $O/pmc_$n.err || { echo "pass failed: $grp (no further pass is started)"; exit 1; }
 done
 python3 - "$O" <<'PY'
 import csv, glob, collections, json, os, sys
