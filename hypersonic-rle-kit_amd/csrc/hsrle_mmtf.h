@@ -18,4 +18,17 @@ struct MmtfPlan
 // enqueue-only: kernels on `st`, nothing else
 hipError_t mmtf_enqueue(const MmtfPlan &p, bool decode, const uint8_t *dIn, uint8_t *dOut, uint8_t *ws, hipStream_t st);
 
+// rle8_mmtf128 (kernels: hsrle_rle8mmtf.hip.h; launched by inst_rle8mmtf.hip).  Workspace, from its 256-byte aligned start: control words, the rank
+// buffer, table A (encode: the span summaries; decode: the packet records), table B (encode: the span results), the mmtf128 plan's workspace.
+struct Rle8MmtfPlan
+{
+  MmtfPlan mmtf;
+  uint32_t size = 0, rows = 0;
+  uint32_t SP = 0, spans = 0;       // encode: rows per span (<= 64), spans
+  uint32_t maxRec = 0;              // decode: records table A can hold
+  uint64_t offRanks = 0, offA = 0, offB = 0, offMmtf = 0, total = 0;
+};
+hipError_t rle8mmtf_compress_enqueue(const Rle8MmtfPlan &p, const uint8_t *dIn, uint8_t *dOut, uint32_t outCap, uint32_t *dOutSize, uint32_t *dStatus, uint8_t *ws, hipStream_t st);
+hipError_t rle8mmtf_decompress_enqueue(const Rle8MmtfPlan &p, const uint8_t *dStream, uint32_t streamCap, uint8_t *dOut, uint32_t *dStatus, uint8_t *ws, hipStream_t st);
+
 }   // namespace hsrle

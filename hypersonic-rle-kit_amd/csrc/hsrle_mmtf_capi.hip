@@ -1,5 +1,7 @@
 // hsrle_mmtf_capi.hip -- C ABI of the mmtf / bitmmtf transforms (include/hsrle.h section 5; reference: src/rle.h:420-438, src/mmtf.c, src/bit_mmtf.c).
 // The plan (segment length, chunk length, workspace layout) is made here on the host from the size alone; inst_mmtf.hip launches it.
+// Behind it: the C ABI of the rle8_mmtf128 codec (reference: src/rle8_mmtf.c, src/rle.h:442-452), which runs the mmtf128 plan between its own passes
+// (kernels: hsrle_rle8mmtf.hip.h, launched by inst_rle8mmtf.hip).
 #include "../../include/hsrle.h"
 
 #include "hsrle_mmtf.h"
@@ -7,6 +9,7 @@
 #include <atomic>
 #include <math.h>
 #include <mutex>
+#include <string.h>
 
 namespace hsrle {
 
@@ -127,11 +130,132 @@ static uint32_t mmtf_dropin(int transform, int decode, const uint8_t *pIn, uint3
   return inSize;
 }
 
+// ---- rle8_mmtf128 (reference: src/rle8_mmtf.c): the mmtf128 plan above between the codec's own passes ----
+static std::atomic<uint32_t> g_rle8MmtfSpanRows{ 0 };
+constexpr uint32_t kRle8MmtfMaxIn = 1u << 30;
+
+static inline uint64_t up256(uint64_t v) { return (v + 255u) & ~255ull; }
+
+static bool rle8mmtf_plan(int decode, uint64_t size, Rle8MmtfPlan &p)
+{
+  if (size == 0u || size > kRle8MmtfMaxIn || !mmtf_plan(HSRLE_MMTF128, size, p.mmtf))
+    return false;
+  p.size = (uint32_t)size;
+  p.rows = p.size / 16u;
+  const uint32_t tuning = g_rle8MmtfSpanRows.load();
+  p.SP = tuning == 0u || tuning > 64u ? 64u : tuning;
+  p.spans = (p.rows + p.SP - 1u) / p.SP;
+  p.maxRec = p.rows + 1u;   // a record per non-null packet, and such a packet holds a row
+  p.offRanks = 256u;
+  p.offA = p.offRanks + up256((uint64_t)p.size + 16u);
+  p.offB = p.offA + up256(16ull * (decode ? p.maxRec : p.spans));
+  p.offMmtf = p.offB + up256(decode ? 0u : 16ull * p.spans);
+  p.total = 256u + p.offMmtf + p.mmtf.total;
+  return true;
+}
+
+static uint32_t rle8mmtf_bounds(uint32_t inSize) { return inSize > kRle8MmtfMaxIn ? 0u : inSize + 8u; }   // rle8_mmtf.c:26-32
+
+// (the device words of a host-pointer call live in the first 256 bytes of the staged workspace)
+static uint32_t rle8mmtf_compress_dropin(const uint8_t *pIn, uint32_t inSize, uint8_t *pOut, uint32_t outSize)
+{
+  if (pIn == nullptr || pOut == nullptr || inSize == 0u || inSize > kRle8MmtfMaxIn || outSize < rle8mmtf_bounds(inSize))
+    return 0;
+  int n = 0, d = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return 0; }
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMmtfMaxDevices) d = 0;
+  MmtfStaging &S = g_mmtfStaging[d];
+  std::lock_guard<std::mutex> lock(S.mu);
+  const uint64_t need = hsrle_rle8_mmtf128_workspace_size(0, inSize);
+  if (need == 0u || !mmtf_grow(&S.in, &S.inSize, (uint64_t)inSize + 64u) || !mmtf_grow(&S.out, &S.outSize, (uint64_t)inSize + 64u) || !mmtf_grow(&S.ws, &S.wsSize, need + 256u))
+    return 0;
+  uint32_t *words = (uint32_t *)S.ws;
+  if (hipMemcpy(S.in, pIn, inSize, hipMemcpyHostToDevice) != hipSuccess) return 0;
+  if (hsrle_rle8_mmtf128_compress_dev_async(S.in, inSize, S.out, (uint64_t)inSize + 64u, words, words + 1, (uint8_t *)S.ws + 256, need, nullptr) != HSRLE_OK) return 0;
+  uint32_t h[2] = { 0u, 1u };
+  if (hipMemcpy(h, words, 8, hipMemcpyDeviceToHost) != hipSuccess) return 0;   // (synchronises the null stream)
+  if (h[1] != HSRLE_RLE8_MMTF_DONE || h[0] == 0u || h[0] > outSize) return 0;
+  if (hipMemcpy(pOut, S.out, h[0], hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  return h[0];
+}
+
+static uint32_t rle8mmtf_decompress_dropin(const uint8_t *pIn, uint32_t inSize, uint8_t *pOut, uint32_t outSize)
+{
+  if (pIn == nullptr || pOut == nullptr || inSize < 8u || outSize == 0u)
+    return 0;
+  uint32_t hdr[2];
+  memcpy(hdr, pIn, 8);
+  const uint32_t expectedOut = hdr[0], expectedIn = hdr[1];
+  if (expectedOut > outSize || expectedIn > inSize || expectedOut == 0u || expectedOut > kRle8MmtfMaxIn || expectedIn < 8u)
+    return 0;
+  int n = 0, d = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return 0; }
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMmtfMaxDevices) d = 0;
+  MmtfStaging &S = g_mmtfStaging[d];
+  std::lock_guard<std::mutex> lock(S.mu);
+  const uint64_t need = hsrle_rle8_mmtf128_workspace_size(1, expectedOut);
+  if (need == 0u || !mmtf_grow(&S.in, &S.inSize, (uint64_t)expectedIn + 64u) || !mmtf_grow(&S.out, &S.outSize, (uint64_t)expectedOut + 64u) || !mmtf_grow(&S.ws, &S.wsSize, need + 256u))
+    return 0;
+  uint32_t *words = (uint32_t *)S.ws;
+  if (hipMemcpy(S.in, pIn, expectedIn, hipMemcpyHostToDevice) != hipSuccess) return 0;
+  if (hsrle_rle8_mmtf128_decompress_dev_async(S.in, expectedIn, S.out, expectedOut, words, (uint8_t *)S.ws + 256, need, nullptr) != HSRLE_OK) return 0;
+  uint32_t status = 1u;
+  if (hipMemcpy(&status, words, 4, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  if (status != HSRLE_RLE8_MMTF_DONE) return 0;
+  if (hipMemcpy(pOut, S.out, expectedOut, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  return expectedOut;
+}
+
 }   // namespace hsrle
 
 using namespace hsrle;
 
 extern "C" {
+
+void hsrle_rle8_mmtf_tuning(uint32_t spanRows) { g_rle8MmtfSpanRows.store(spanRows); }
+
+uint64_t hsrle_rle8_mmtf128_workspace_size(int decode, uint64_t size)
+{
+  Rle8MmtfPlan p;
+  return rle8mmtf_plan(decode != 0, size, p) ? p.total : 0u;
+}
+
+int hsrle_rle8_mmtf128_compress_dev_async(const void *dIn, uint64_t inSize, void *dOut, uint64_t outCapacity, uint32_t *dOutSize, uint32_t *dStatus, void *dWorkspace,
+                                          uint64_t workspaceSize, void *stream)
+{
+  Rle8MmtfPlan p;
+  if (dIn == nullptr || dOut == nullptr || dOutSize == nullptr || dStatus == nullptr || dWorkspace == nullptr || !rle8mmtf_plan(false, inSize, p))
+    return HSRLE_ERR_ARGUMENT;
+  const uintptr_t a = (uintptr_t)dIn, b = (uintptr_t)dOut;
+  if ((a < b + outCapacity && b < a + inSize) || (((uintptr_t)dOutSize | (uintptr_t)dStatus) & 3u) != 0u)
+    return HSRLE_ERR_ARGUMENT;
+  if (outCapacity < inSize + 8u || workspaceSize < p.total)
+    return HSRLE_ERR_CAPACITY;
+  uint8_t *ws = (uint8_t *)(((uintptr_t)dWorkspace + 255u) & ~(uintptr_t)255u);
+  const uint32_t cap = outCapacity > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)outCapacity;
+  return rle8mmtf_compress_enqueue(p, (const uint8_t *)dIn, (uint8_t *)dOut, cap, dOutSize, dStatus, ws, (hipStream_t)stream) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
+}
+
+int hsrle_rle8_mmtf128_decompress_dev_async(const void *dStream, uint64_t streamSize, void *dOut, uint64_t outSize, uint32_t *dStatus, void *dWorkspace, uint64_t workspaceSize,
+                                            void *stream)
+{
+  Rle8MmtfPlan p;
+  if (dStream == nullptr || dOut == nullptr || dStatus == nullptr || dWorkspace == nullptr || streamSize == 0u || !rle8mmtf_plan(true, outSize, p))
+    return HSRLE_ERR_ARGUMENT;
+  const uintptr_t a = (uintptr_t)dStream, b = (uintptr_t)dOut;
+  if ((a < b + outSize && b < a + streamSize) || ((uintptr_t)dStatus & 3u) != 0u)
+    return HSRLE_ERR_ARGUMENT;
+  if (workspaceSize < p.total)
+    return HSRLE_ERR_CAPACITY;
+  uint8_t *ws = (uint8_t *)(((uintptr_t)dWorkspace + 255u) & ~(uintptr_t)255u);
+  const uint32_t cap = streamSize > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)streamSize;
+  return rle8mmtf_decompress_enqueue(p, (const uint8_t *)dStream, cap, (uint8_t *)dOut, dStatus, ws, (hipStream_t)stream) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
+}
+
+uint32_t rle8_mmtf128_compress_bounds(const uint32_t inSize) { return rle8mmtf_bounds(inSize); }
+uint32_t rle8_mmtf256_compress_bounds(const uint32_t inSize) { return rle8mmtf_bounds(inSize); }
+uint32_t rle8_mmtf128_compress(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize) { return rle8mmtf_compress_dropin(pIn, inSize, pOut, outSize); }
+uint32_t rle8_mmtf128_decompress(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize) { return rle8mmtf_decompress_dropin(pIn, inSize, pOut, outSize); }
 
 void hsrle_mmtf_tuning(uint32_t segmentRows) { g_mmtfSegmentRows.store(segmentRows); }
 

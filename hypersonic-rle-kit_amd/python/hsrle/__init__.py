@@ -178,6 +178,17 @@ def _lib():
     for nm in ("mmtf_bounds", "bitmmtf_bounds"):
         getattr(L, nm).restype = u32
         getattr(L, nm).argtypes = [u32]
+    for nm in ("rle8_mmtf128_compress_bounds", "rle8_mmtf256_compress_bounds"):
+        getattr(L, nm).restype = u32
+        getattr(L, nm).argtypes = [u32]
+    L.hsrle_rle8_mmtf128_workspace_size.restype = u64
+    L.hsrle_rle8_mmtf128_workspace_size.argtypes = [ci, u64]
+    L.hsrle_rle8_mmtf128_compress_dev_async.restype = ci
+    L.hsrle_rle8_mmtf128_compress_dev_async.argtypes = [vp, u64, vp, u64, vp, vp, vp, u64, vp]
+    L.hsrle_rle8_mmtf128_decompress_dev_async.restype = ci
+    L.hsrle_rle8_mmtf128_decompress_dev_async.argtypes = [vp, u64, vp, u64, vp, vp, u64, vp]
+    L.hsrle_rle8_mmtf_tuning.restype = None
+    L.hsrle_rle8_mmtf_tuning.argtypes = [u32]
     _LIB = L
     return L
 
@@ -802,3 +813,62 @@ mmtf128_encode, mmtf128_decode = _mmtf_dropin("mmtf128_encode"), _mmtf_dropin("m
 mmtf256_encode, mmtf256_decode = _mmtf_dropin("mmtf256_encode"), _mmtf_dropin("mmtf256_decode")
 bitmmtf8_encode, bitmmtf8_decode = _mmtf_dropin("bitmmtf8_encode"), _mmtf_dropin("bitmmtf8_decode")
 bitmmtf16_encode, bitmmtf16_decode = _mmtf_dropin("bitmmtf16_encode"), _mmtf_dropin("bitmmtf16_decode")
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# rle8_mmtf128: mmtf128 + run-length coding over rank rows + bit packing (include/hsrle.h section 5; reference: src/rle8_mmtf.c)
+
+RLE8_MMTF_DONE, RLE8_MMTF_MALFORMED, RLE8_MMTF_CAPACITY = 0, 1, 2
+
+
+def rle8_mmtf128_compress_bounds(n):
+    return int(_lib().rle8_mmtf128_compress_bounds(n))
+
+
+def rle8_mmtf256_compress_bounds(n):
+    return int(_lib().rle8_mmtf256_compress_bounds(n))
+
+
+def rle8_mmtf128_compress(data, out_cap=None):
+    """The reference-named host-pointer function: returns (return value, stream[:return value]).  out_cap defaults to the reference's bound + 5 (the
+    bound itself is 5 bytes short for incompressible input, include/hsrle.h)."""
+    data = bytes(data)
+    return call_dropin("rle8_mmtf128_compress", data, rle8_mmtf128_compress_bounds(len(data)) + 5 if out_cap is None else out_cap)
+
+
+def rle8_mmtf128_decompress(stream, out_cap):
+    """The reference-named host-pointer function: returns (return value, output[:return value])."""
+    return call_dropin("rle8_mmtf128_decompress", bytes(stream), out_cap)
+
+
+def rle8_mmtf128_workspace_size(decode, size):
+    """hsrle_rle8_mmtf128_workspace_size: bytes of device workspace for `size` uncompressed bytes (0: size == 0 or above 2^30)."""
+    return int(_lib().hsrle_rle8_mmtf128_workspace_size(1 if decode else 0, size))
+
+
+def rle8_mmtf_tuning(span_rows=0):
+    """hsrle_rle8_mmtf_tuning: rows per wave span of the compress passes (1 .. 64; 0 = 64).  Process-global, for tests."""
+    _lib().hsrle_rle8_mmtf_tuning(span_rows)
+
+
+def rle8_mmtf128_compress_dev(src, dst, out_size, status, ws, stream=None):
+    """hsrle_rle8_mmtf128_compress_dev_async: enqueue the compression of the CUDA uint8 tensor `src` into `dst` (>= src.numel() + 8 bytes; + 13 always
+    suffice).  out_size / status: CUDA int32 tensors of one element, they receive the stream size and RLE8_MMTF_DONE / RLE8_MMTF_CAPACITY."""
+    for t, what in ((src, "src"), (dst, "dst"), (ws, "ws")):
+        _check_u8_cuda(t, what)
+    rc = _lib().hsrle_rle8_mmtf128_compress_dev_async(ctypes.c_void_p(src.data_ptr()), src.numel(), ctypes.c_void_p(dst.data_ptr()), dst.numel(),
+                                                      ctypes.c_void_p(out_size.data_ptr()), ctypes.c_void_p(status.data_ptr()),
+                                                      ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(stream))
+    if rc != OK:
+        raise HsrleError(rc, "hsrle_rle8_mmtf128_compress_dev_async")
+
+
+def rle8_mmtf128_decompress_dev(src, dst, status, ws, stream=None):
+    """hsrle_rle8_mmtf128_decompress_dev_async: enqueue the decompression of the stream in the CUDA uint8 tensor `src` into `dst`, whose numel() is the
+    uncompressed size.  status: CUDA int32 tensor of one element, receives RLE8_MMTF_DONE / RLE8_MMTF_MALFORMED."""
+    for t, what in ((src, "src"), (dst, "dst"), (ws, "ws")):
+        _check_u8_cuda(t, what)
+    rc = _lib().hsrle_rle8_mmtf128_decompress_dev_async(ctypes.c_void_p(src.data_ptr()), src.numel(), ctypes.c_void_p(dst.data_ptr()), dst.numel(),
+                                                        ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(stream))
+    if rc != OK:
+        raise HsrleError(rc, "hsrle_rle8_mmtf128_decompress_dev_async")

@@ -605,7 +605,8 @@ int hsrle_rle8m_decompress_dev_async(const void *dStream, const hsrle_rle8m_info
 /* inSize % 16 (32) bytes behind the last whole row are looked up without an update.  bitmmtf8 / bitmmtf16: XOR with the previous byte /  */
 /* little-endian 16 bit word (an odd last byte of bitmmtf16 is copied).  Same names, arguments and return values as the reference: inSize */
 /* on success, 0 for inSize == 0, inSize > outSize, a NULL pointer or no usable device.  Host pointers, staged per device like section 1. */
-/* Still open of rle.h: rle8_mmtf128_* / rle8_mmtf256_* (RLE + MMTF + bit packing, rle.h:442-452) and rle8_sh_*.                           */
+/* rle8_mmtf128_* (RLE + MMTF + bit packing, rle.h:442-452) follows below.  Still open of rle.h: rle8_sh_*, and rle8_mmtf256_compress /    */
+/* _decompress, which the reference declares and never defines.                                                                            */
 uint32_t mmtf_bounds(const uint32_t inSize);
 uint32_t mmtf128_encode(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize);
 uint32_t mmtf128_decode(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize);
@@ -635,6 +636,56 @@ uint32_t bitmmtf16_decode(const uint8_t *pIn, const uint32_t inSize, uint8_t *pO
 uint64_t hsrle_mmtf_workspace_size(int transform, uint64_t size);
 int hsrle_mmtf_dev_async(int transform, int decode, const void *dIn, uint64_t size, void *dOut, void *dWorkspace, uint64_t workspaceSize, void *stream);
 void hsrle_mmtf_tuning(uint32_t segmentRows);
+
+/*
+ * rle8_mmtf128 (src/rle8_mmtf.c, rle.h:442-452): the mmtf128 transform, run-length coding over the 16-byte rank rows, 2 / 3 / 4 bit packing of the
+ * literal rows -- one stream: u32 inSize, u32 streamSize, COPY and RLE packets in turn, the inSize % 16 tail ranks (csrc/hsrle_rle8mmtf.hip.h has the
+ * grammar).  Same names, arguments and return values as the reference.  bounds: 0 above 2^30, else inSize + 8.  compress: the stream's size; 0 for a
+ * NULL pointer, inSize == 0, outSize < bounds.  decompress: the header's inSize; 0 for a NULL pointer, a zero size, header sizes larger than the
+ * arguments.  rle8_mmtf256_compress / _decompress are only declared by the reference (no body anywhere) and are NOT exported; the bounds function is.
+ * Where this library differs, on purpose:
+ *  - THE FIRST PACKET'S WIDTH.  The reference ORs an undefined start value (_mm_undefined_si128, rle8_mmtf.c:182) into the width decision of the first
+ *    COPY packet, so its first packet may be wider than its rows need, differently from build to build.  Here the start value is ZERO: the first
+ *    packet gets the narrowest width its rows allow (a first COPY of no rows is the byte 0x06).  Whenever a row of the first packet holds a rank
+ *    >= 16 the reference is deterministic too and the streams are equal byte for byte; otherwise they are equal from the end of the first COPY
+ *    packet on, and each side decodes the other's stream.
+ *  - compress returns 0 for inSize > 2^30 (the reference's bound is 0 there and it runs on).
+ *  - The reference's bound forgets the 8 header bytes: incompressible input of 32 rows or more needs up to inSize + 13 and the reference writes
+ *    past outSize.  compress returns 0 when the stream does not fit in outSize; inSize + 13 bytes always suffice.
+ *  - decompress checks every packet against streamSize and the row count BEFORE anything is written and returns 0 for a malformed stream (a packet
+ *    past the stream's end or the last row, a chain that has not ended when the rows are used up, rows left over, inSize < 8); the reference does
+ *    not check.
+ * Host pointers, staged per device like the functions above.
+ */
+uint32_t rle8_mmtf128_compress_bounds(const uint32_t inSize);
+uint32_t rle8_mmtf256_compress_bounds(const uint32_t inSize);
+uint32_t rle8_mmtf128_compress(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize);
+uint32_t rle8_mmtf128_decompress(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize);
+
+/*
+ * The same, device resident and ENQUEUE-ONLY (nothing allocates, synchronises or reads device memory; a HIP graph can capture the calls; nothing is
+ * zeroed, every word the kernels read is written by a kernel before).  Buffers at any byte address, not overlapping; dOutSize / dStatus: device words,
+ * 4-byte aligned.  dWorkspace >= hsrle_rle8_mmtf128_workspace_size(decode, uncompressed size) bytes, contents do not matter: the rank buffer (the
+ * uncompressed size), 16 bytes per span of 64 rows twice (compress) or 16 bytes per row for the packet records (decompress), the mmtf128 workspace.
+ * compress: 1 <= inSize <= 2^30 and outCapacity >= inSize + 8, else HSRLE_ERR_ARGUMENT / HSRLE_ERR_CAPACITY and nothing is enqueued.  *dOutSize
+ *   receives the stream's size and *dStatus HSRLE_RLE8_MMTF_DONE, or 0 and HSRLE_RLE8_MMTF_CAPACITY when the stream is larger than outCapacity (see
+ *   above; then nothing is written to dOut).
+ * decompress: outSize is the UNCOMPRESSED size, which the caller knows (the stream's first word): the mmtf128 decode is planned from it on the host.
+ *   The header is read on the device; *dStatus receives HSRLE_RLE8_MMTF_DONE, or HSRLE_RLE8_MMTF_MALFORMED (header inSize != outSize, header
+ *   streamSize > streamSize, or a chain as described above); then dOut[0, outSize) holds nothing of use.  Never more than outSize bytes are written.
+ *   The header chain is followed by ONE wave (the format's one serial dependence): its time grows with the number of packets, not the bytes.
+ * hsrle_rle8_mmtf_tuning: rows per wave span of the compress passes, 1 .. 64 (0 or more = 64).  Any value gives the same bytes.  PROCESS-GLOBAL,
+ * for tests; it changes the workspace size.  hsrle_mmtf_tuning acts on the mmtf128 passes inside as it does on their own.
+ */
+#define HSRLE_RLE8_MMTF_DONE 0
+#define HSRLE_RLE8_MMTF_MALFORMED 1
+#define HSRLE_RLE8_MMTF_CAPACITY 2
+uint64_t hsrle_rle8_mmtf128_workspace_size(int decode, uint64_t size);
+int hsrle_rle8_mmtf128_compress_dev_async(const void *dIn, uint64_t inSize, void *dOut, uint64_t outCapacity, uint32_t *dOutSize, uint32_t *dStatus, void *dWorkspace,
+                                          uint64_t workspaceSize, void *stream);
+int hsrle_rle8_mmtf128_decompress_dev_async(const void *dStream, uint64_t streamSize, void *dOut, uint64_t outSize, uint32_t *dStatus, void *dWorkspace, uint64_t workspaceSize,
+                                            void *stream);
+void hsrle_rle8_mmtf_tuning(uint32_t spanRows);
 
 int hsrle_kernel_waves_per_cu(int codec, int decode);
 const char *hsrle_version(void);
