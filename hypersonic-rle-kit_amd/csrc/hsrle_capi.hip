@@ -32,6 +32,8 @@
 // ====================================================================================================================
 using namespace hsrle;
 
+#include "hsrle_capi_mmtf.h"                // the mmtf / bitmmtf transforms and rle8_mmtf128: plans, their C ABI, their host-pointer functions
+
 extern "C" {
 
 int hsrle_codec_from_name(const char *name)
@@ -73,8 +75,8 @@ int hsrle_kernel_waves_per_cu(int codec, int decode)
     return 0;
   init_tables();
   int n = 0;
-  if (decode) { DecodeArgs a{}; a.residentWorkgroups = &n; if (g_dec[codec](a, nullptr) != hipSuccess) return 0; }
-  else { EncodeArgs a{}; a.residentWorkgroups = &n; if (g_enc[codec](a, nullptr) != hipSuccess) return 0; }
+  if (decode) { DecodeArgs a{}; a.residentWorkgroups = &n; if (g_launch[codec].dec(a, nullptr) != hipSuccess) return 0; }
+  else { EncodeArgs a{}; a.residentWorkgroups = &n; if (g_launch[codec].enc(a, nullptr) != hipSuccess) return 0; }
   return n;
 }
 
@@ -543,7 +545,7 @@ int hsrle_compress_mono_dev_async(int codec, const void *dIn, uint32_t inSize, v
   if (outCapacity < bounds32(inSize)) return HSRLE_ERR_CAPACITY;
   if (!device_ok()) return HSRLE_ERR_DEVICE;
   const MonoEncPlan m = plan_mono_encode(inSize, codec);
-  if (!g_ppw[codec] || !m.windowed) return HSRLE_ERR_UNSUPPORTED;         // (the 8 bit pair only, as ever: the other codecs take hsrle_compress_mono_dev_enqueue)
+  if (!g_launch[codec].ppw8 || !m.windowed) return HSRLE_ERR_UNSUPPORTED;         // (the 8 bit pair only, as ever: the other codecs take hsrle_compress_mono_dev_enqueue)
   if (workspaceSize < m.total) return HSRLE_ERR_CAPACITY;
   return mono_encode_dev(codec, (const uint8_t *)dIn, inSize, (uint8_t *)dOut, (uint8_t *)dWorkspace, m, nullptr, dStreamSize, (hipStream_t)stream);
 }
@@ -703,7 +705,7 @@ int hsrle_mono_decompress_range_dev_async(const void *dStream, const void *dInde
     return HSRLE_OK;
   if (!device_ok()) return HSRLE_ERR_DEVICE;
   init_tables();
-  if (!g_dec[mh.codec])
+  if (!g_launch[mh.codec].dec)
     return HSRLE_ERR_UNSUPPORTED;
   const hipStream_t st = (hipStream_t)stream;
   const uint32_t B = info->spacing, first = (uint32_t)(offset / B), n = (uint32_t)((offset + length - 1u) / B) - first + 1u;
@@ -717,7 +719,7 @@ int hsrle_mono_decompress_range_dev_async(const void *dStream, const void *dInde
   // stops every workgroup (a decode error seen by an early workgroup may stop later ones too -- the result is MALFORMED either way)
   DecodeArgs da{ (const uint8_t *)dStream, nullptr, (const uint8_t *)dStream + mh.C + HSRLE_CONTAINER_TAIL_PAD, (uint8_t *)dOut, mh.U, B, first, n, dStatus };
   da.entries = rec; da.entryBase = 0; da.gate = dStatus; da.gateWords = 1; da.winLo = offset; da.winHi = offset + length;
-  if (g_dec[mh.codec](da, st) != hipSuccess) return HSRLE_ERR_DEVICE;
+  if (g_launch[mh.codec].dec(da, st) != hipSuccess) return HSRLE_ERR_DEVICE;
   hipLaunchKernelGGL(k_range_status, dim3(1), dim3(1), 0, st, dStatus);
   return hipGetLastError() == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
 }
@@ -735,7 +737,7 @@ int hsrle_decompress_range_dev_async(const void *dContainer, const hsrle_contain
     return HSRLE_OK;
   if (!device_ok()) return HSRLE_ERR_DEVICE;
   init_tables();
-  if (!g_dec[info->codec])
+  if (!g_launch[info->codec].dec)
     return HSRLE_ERR_UNSUPPORTED;
   const hipStream_t st = (hipStream_t)stream;
   const uint32_t first = (uint32_t)(offset / info->blockSize), n = (uint32_t)((offset + length - 1u) / info->blockSize) - first + 1u;
@@ -745,7 +747,7 @@ int hsrle_decompress_range_dev_async(const void *dContainer, const hsrle_contain
   DecodeArgs da{ payload, (const uint64_t *)(container + HSRLE_CONTAINER_HEADER_SIZE), payload + info->payloadSize + HSRLE_CONTAINER_TAIL_PAD,
                  (uint8_t *)dOut, info->uncompressedSize, info->blockSize, first, n, dStatus };
   da.winLo = offset; da.winHi = offset + length;
-  if (g_dec[info->codec](da, st) != hipSuccess) return HSRLE_ERR_DEVICE;
+  if (g_launch[info->codec].dec(da, st) != hipSuccess) return HSRLE_ERR_DEVICE;
   hipLaunchKernelGGL(k_range_status, dim3(1), dim3(1), 0, st, dStatus);
   return hipGetLastError() == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
 }

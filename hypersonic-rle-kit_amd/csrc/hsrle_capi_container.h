@@ -131,9 +131,9 @@ static uint32_t split_pieces(uint32_t B)
   return (k == kSplitPiecesMax && B % (kSplitPiecesMax * 128u) == 0u) ? k : kSplitPieces;
 }
 
-// (round 6: the codecs with a position-parallel encoder have no run list instantiation any more -- hsrle_inst_generic.inc: pp_covers; callers run behind init_tables())
+// (round 6: the codecs with a position-parallel encoder -- a pp launcher in their row -- have no run list instantiation any more; callers run behind init_tables())
 // (the codecs with a run list instantiation were: all but Single, 128 bit and Greedy)
-static bool run_list_codec(int codec) { const CodecInfo &ci = kCodecs[codec]; return !is_single(ci) && ci.S != 16 && !ci.greedy && !g_pp[codec]; }
+static bool run_list_codec(int codec) { const CodecInfo &ci = kCodecs[codec]; return !is_single(ci) && ci.S != 16 && !ci.greedy && !g_launch[codec].pp; }
 
 static bool split_encode_applies(int codec, uint64_t nBlocks, uint32_t B)
 {
@@ -148,7 +148,7 @@ static bool split_encode_applies(int codec, uint64_t nBlocks, uint32_t B)
   if (ci.greedy && !greedy_one_symbol_list(ci)) return false;
   if (is_single(ci) && B > 32768u) return false;   // (the per-block symbol pick holds a block in LDS: hsrle_encode8s.hip.h)
   init_tables();
-  return g_menc[codec] != nullptr;
+  return g_launch[codec].menc != nullptr;
 }
 
 // Split encode of a container (no host synchronisation: graph capturable like the plain path): cuts inside the blocks -> chunk table (block
@@ -181,7 +181,7 @@ static int compress_split(int codec, const uint8_t *dIn, uint64_t U, uint32_t B,
     MonoEncodeArgs pm{ nullptr, nullptr, nullptr, 0u };
     pm.pick = pickTable; pm.phase = 1u;
     pm.cutPos = cutPos; pm.cutSym = cutSym; pm.cutFlags = flags; pm.cutG = G; pm.cutLong = longc;   // (... and the blocks' cuts, by the same waves: the block is in LDS there)
-    if (g_menc[codec](pa, pm, st) != hipSuccess)
+    if (g_launch[codec].menc(pa, pm, st) != hipSuccess)
       return HSRLE_ERR_DEVICE;
   }
   if (!single) launch_cuts(S, ci.aligned, nullptr, cgrid, st, dIn, U, G, pieces, longc, cutPos, cutSym, flags, B);   // (Single: the pick above left the cuts)
@@ -201,7 +201,7 @@ static int compress_split(int codec, const uint8_t *dIn, uint64_t U, uint32_t B,
   ma.listOut = listK ? listOut : nullptr;
   ma.pick = pickTable;                                                 // (8 bit Single: the blocks' symbols)
   if (single) { ma.jobs = (uint64_t *)(ws + w.spJobs); ma.jobCount = ctrl + 12; ma.jobCap = (uint32_t)(w.spJobCap < 0xFFFFFFFFull ? w.spJobCap : 0xFFFFFFFFull); }   // (ctrl[12]: zeroed above)
-  if (g_menc[codec](ea, ma, st) != hipSuccess)
+  if (g_launch[codec].menc(ea, ma, st) != hipSuccess)
     return HSRLE_ERR_DEVICE;
   if (listK != 0 && !inKernelLists)
   {
@@ -214,14 +214,14 @@ static int compress_split(int codec, const uint8_t *dIn, uint64_t U, uint32_t B,
     hipLaunchKernelGGL(k_split_list_guess, dim3((maxChunks + 255u) / 256u), dim3(256), 0, st, guess, (const uint64_t *)listOut, (const uint64_t *)starts, (const uint32_t *)ctrl, B, (uint32_t)listK, (uint32_t)S,
                        ctrl + 8);
     ma.steps = base | (1u << 16);
-    if (g_menc[codec](ea, ma, st) != hipSuccess)
+    if (g_launch[codec].menc(ea, ma, st) != hipSuccess)
       return HSRLE_ERR_DEVICE;
     for (uint32_t round = 0; round + 1u < ppb; round++)
     {
       hipLaunchKernelGGL(k_split_list_verify, dim3((maxChunks + 255u) / 256u), dim3(256), 0, st, guess, (const uint64_t *)listOut, (const uint64_t *)starts, (const uint32_t *)ctrl, B, (uint32_t)listK,
                          (uint32_t)S, ctrl + 9 + round);
       ma.steps = base | ((2u + round) << 16);
-      if (g_menc[codec](ea, ma, st) != hipSuccess)                       // (chunks whose list was right are switched off: word 7 of their guess)
+      if (g_launch[codec].menc(ea, ma, st) != hipSuccess)                       // (chunks whose list was right are switched off: word 7 of their guess)
         return HSRLE_ERR_DEVICE;
     }
   }
@@ -246,7 +246,7 @@ constexpr uint32_t kPpMinBlocks = 1u;       // (faster than the ring and the run
 static bool pp_applies(int codec, uint32_t nBlocks, uint32_t B)
 {
   static const uint32_t force = knob_u32("HSRLE_PP", 0u);
-  if (codec < 0 || codec >= kCodecCount || !g_pp[codec] || B > kPpMaxBlock || force == 2u) return false;
+  if (codec < 0 || codec >= kCodecCount || !g_launch[codec].pp || B > kPpMaxBlock || force == 2u) return false;
   // (the slot area holds the records: pp_scratch_bytes() is less than nBlocks staging slots for every block size)
   return force == 1u || nBlocks >= kPpMinBlocks;
 }
@@ -258,8 +258,13 @@ static bool pp_applies(int codec, uint32_t nBlocks, uint32_t B)
 #endif
 constexpr uint32_t kPpwMinBlocks = HSRLE_PPW_MIN_BLOCKS;   // (A/B builds: 0xFFFFFFFF = never, also for the monolithic streams)
 // words of a window's state record: the 8 bit pair 8, the codecs of hsrle_encodeSp.hip.h 16, those of hsrle_encodeLp.hip.h (the list travels with it) 32
-static uint32_t ppw_state_words(int codec) { return g_ppw[codec] ? kPpwStateWords : (g_ppwL[codec] ? kPpwLStateWords : kPpwSStateWords); }
-static PpwLaunch ppw_launcher(int codec) { return (codec < 0 || codec >= kCodecCount) ? nullptr : (g_ppw[codec] ? g_ppw[codec] : (g_ppwL[codec] ? g_ppwL[codec] : g_ppwS[codec])); }
+static uint32_t ppw_state_words(int codec) { const CodecLaunch &l = g_launch[codec]; return l.ppw8 ? kPpwStateWords : (l.ppwL ? kPpwLStateWords : kPpwSStateWords); }
+static PpwLaunch ppw_launcher(int codec)
+{
+  if (codec < 0 || codec >= kCodecCount) return nullptr;
+  const CodecLaunch &l = g_launch[codec];
+  return l.ppw8 ? l.ppw8 : (l.ppwL ? l.ppwL : l.ppwS);
+}
 // (the plain / Packed codecs write 8 or 32 bit fields whatever the block size; the LUT / Short forms choose their field widths -- and the reference its penalties, with
 //  thresholds of 0xFFFFF: rleX_Xsl.h:130, rleX_Xsl_short.h:178 -- by the values: below 1 MiB per block no count or range gets there and "every run is stored" holds)
 constexpr uint32_t kPpwListMaxBlock = (1u << 20) - 128u;
@@ -287,7 +292,7 @@ static int compress_async(int codec, const void *dIn, uint64_t U, void *dOut, ui
     return HSRLE_ERR_DEVICE;
 
   init_tables();
-  if (!g_enc[codec])
+  if (!g_launch[codec].enc)
     return HSRLE_ERR_UNSUPPORTED;
 
   // (8 bit Single / 128 bit, small containers of 1 .. 4 KiB blocks: the split encode needs regions the general workspace does not reserve --
@@ -329,14 +334,14 @@ static int compress_async(int codec, const void *dIn, uint64_t U, void *dOut, ui
   hipStream_t aux = w.nChunks > 1 ? aux_stream() : nullptr;
 #ifdef HSRLE_EXPERIMENTS
   static const bool waveEncode = env_u32("HSRLE_ENCODE_WAVE", 0) != 0u;
-  if (waveEncode && g_wenc[codec] && B <= kWaveEncodeMaxBlock)
+  if (waveEncode && g_launch[codec].wenc && B <= kWaveEncodeMaxBlock)
   {
     // (the slot area of the lane-per-block path is not needed: the tile words and the ticket counters live at its start)
     uint32_t *ticket = (uint32_t *)(ws + w.offSlots);
     unsigned long long *tiles = (unsigned long long *)(ws + w.offSlots + kTicketBytes);
     WaveEncodeArgs wa{ (const uint8_t *)dIn, U, B, nBlocks, offsets, payload, tiles, ticket };
     if (w.offSizes - w.offSlots < kTicketBytes + 8ull * nBlocks) rc = HSRLE_ERR_CAPACITY;
-    else if (zero_async(ticket, kTicketBytes + 8ull * nBlocks, st) != hipSuccess || g_wenc[codec](wa, st) != hipSuccess)
+    else if (zero_async(ticket, kTicketBytes + 8ull * nBlocks, st) != hipSuccess || g_launch[codec].wenc(wa, st) != hipSuccess)
       rc = HSRLE_ERR_DEVICE;
   }
   else
@@ -346,7 +351,7 @@ static int compress_async(int codec, const void *dIn, uint64_t U, void *dOut, ui
     // position-parallel encoder (hsrle_encode8p.hip.h): sizes + one record per stored run, scan, then every stream written once to its final place --
     // no staging slots, no compaction.  The records live in the (otherwise unused) slot area.
     PpArgs pa{ (const uint8_t *)dIn, U, B, nBlocks, sizes, offsets, payload, ws + w.offSlots };
-    if (g_pp[codec](pa, 0, st) != hipSuccess)
+    if (g_launch[codec].pp(pa, 0, st) != hipSuccess)
       rc = HSRLE_ERR_DEVICE;
     else if (nBlocks <= kScanSmallMax && (((uintptr_t)sizes) & 15u) == 0u)   // (the one-launch scan reads the sizes 16 bytes at a time: a caller's workspace may sit anywhere)
     {
@@ -355,7 +360,7 @@ static int compress_async(int codec, const void *dIn, uint64_t U, void *dOut, ui
     }
     else if (scan_sizes(sizes, nBlocks, offsets, ws, w.levels, st) != hipSuccess)
       rc = HSRLE_ERR_DEVICE;
-    if (rc == HSRLE_OK && g_pp[codec](pa, 1, st) != hipSuccess)
+    if (rc == HSRLE_OK && g_launch[codec].pp(pa, 1, st) != hipSuccess)
       rc = HSRLE_ERR_DEVICE;
   }
   else if (w.nChunks <= 1 && ppw_applies(codec, nBlocks, B))
@@ -391,7 +396,7 @@ static int compress_async(int codec, const void *dIn, uint64_t U, void *dOut, ui
   {
     EncodeArgs ea{ (const uint8_t *)dIn, U, B, nBlocks, ws + w.offSlots, stride, sizes };
     ea.ringSel = (uint32_t *)(ws + w.offSlots + align_up((uint64_t)nBlocks * stride, 256));   // (in the wave encoder's counter area behind the slots: unused on this path)
-    if (g_enc[codec](ea, st) != hipSuccess)
+    if (g_launch[codec].enc(ea, st) != hipSuccess)
       rc = HSRLE_ERR_DEVICE;
     else if (nBlocks <= kScanSmallMax && (((uintptr_t)sizes) & 15u) == 0u)   // (the one-launch scan reads the sizes 16 bytes at a time: a caller's workspace may sit anywhere)
     {
@@ -417,7 +422,7 @@ static int compress_async(int codec, const void *dIn, uint64_t U, void *dOut, ui
       uint8_t *slots = ws + w.offSlots + (k & 1u) * w.chunk * (uint64_t)stride;
       if (k >= 2) ok = hipStreamWaitEvent(st, compacted[k & 1u], 0) == hipSuccess;
       EncodeArgs ea{ (const uint8_t *)dIn + first * B, U - first * B, B, count, slots, stride, sizes + first };
-      ok = ok && g_enc[codec](ea, st) == hipSuccess && scan_sizes(sizes + first, count, offsets + first, ws, w.levels, st, k ? offsets + first : nullptr) == hipSuccess &&
+      ok = ok && g_launch[codec].enc(ea, st) == hipSuccess && scan_sizes(sizes + first, count, offsets + first, ws, w.levels, st, k ? offsets + first : nullptr) == hipSuccess &&
            hipEventRecord(scanned, st) == hipSuccess && hipStreamWaitEvent(aux, scanned, 0) == hipSuccess;
       if (!ok) break;
       hipLaunchKernelGGL(k_compact, dim3((count + 3u) / 4u), dim3(256), 0, aux, (const uint8_t *)slots, stride, (const uint64_t *)(offsets + first), payload, count);
@@ -478,14 +483,14 @@ static int decompress_blocks_async(const void *dContainer, const hsrle_container
     return HSRLE_OK;
 
   init_tables();
-  if (!g_dec[info->codec])
+  if (!g_launch[info->codec].dec)
     return HSRLE_ERR_UNSUPPORTED;
 
   const uint8_t *container = (const uint8_t *)dContainer;
   const uint8_t *payload = container + HSRLE_CONTAINER_HEADER_SIZE + 8ull * ((uint64_t)info->blockCount + 1ull);
   DecodeArgs da{ payload, (const uint64_t *)(container + HSRLE_CONTAINER_HEADER_SIZE), payload + info->payloadSize + HSRLE_CONTAINER_TAIL_PAD,
                  (uint8_t *)dOut, info->uncompressedSize, info->blockSize, first, count, dStatus };
-  return g_dec[info->codec](da, st) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
+  return g_launch[info->codec].dec(da, st) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -537,7 +542,7 @@ static int decompress_split_async(const void *dContainer, const hsrle_container_
   if (count == 0)
     return HSRLE_OK;
   init_tables();
-  if (!g_dec[info->codec] || !g_sub[info->codec])
+  if (!g_launch[info->codec].dec || !g_launch[info->codec].sub)
     return HSRLE_ERR_UNSUPPORTED;
 
   if (SB == HSRLE_SPLIT_PACKET_LIST)
@@ -549,7 +554,7 @@ static int decompress_split_async(const void *dContainer, const hsrle_container_
     const uint8_t *payload = container + HSRLE_CONTAINER_HEADER_SIZE + 8ull * ((uint64_t)info->blockCount + 1ull);
     DecodeArgs da{ payload, (const uint64_t *)(container + HSRLE_CONTAINER_HEADER_SIZE), payload + info->payloadSize + HSRLE_CONTAINER_TAIL_PAD,
                    (uint8_t *)dOut, info->uncompressedSize, info->blockSize, first, count, dStatus };
-    if (g_sub[info->codec](da, kSubPacketList, (uint32_t *)dWs, st) != hipSuccess)
+    if (g_launch[info->codec].sub(da, kSubPacketList, (uint32_t *)dWs, st) != hipSuccess)
       return HSRLE_ERR_DEVICE;
     return launch_expand_packets(kCodecs[info->codec].S, da, (const uint64_t *)((const uint8_t *)dWs + countsBytes), (const uint32_t *)dWs, st) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
   }
@@ -570,11 +575,11 @@ static int decompress_split_async(const void *dContainer, const hsrle_container_
                  (uint8_t *)dOut, info->uncompressedSize, info->blockSize, first, count, dStatus };
   // records are indexed by the global sub-block number: hand the kernel the address record 0 would have
   uint32_t *rec0 = (uint32_t *)((uintptr_t)dWs - (uintptr_t)(subFirst * 4ull * kEntryRecDwords));
-  if (g_sub[info->codec](da, SB, rec0, st) != hipSuccess)
+  if (g_launch[info->codec].sub(da, SB, rec0, st) != hipSuccess)
     return HSRLE_ERR_DEVICE;
   da.B = SB; da.firstBlock = (uint32_t)subFirst; da.blockCount = (uint32_t)(subEnd - subFirst);
   da.entries = (const uint32_t *)dWs; da.entryBase = (uint32_t)subFirst;
-  return g_dec[info->codec](da, st) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
+  return g_launch[info->codec].dec(da, st) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
 }
 
 // one WAVE per block (experiments/hsrle_decode_wave.hip.h): for containers with too few blocks to fill the chip with one lane each
@@ -596,13 +601,13 @@ static int decompress_wave_async(const void *dContainer, const hsrle_container_i
   if (count == 0)
     return HSRLE_OK;
   init_tables();
-  if (!g_sub[info->codec])
+  if (!g_launch[info->codec].sub)
     return HSRLE_ERR_UNSUPPORTED;
   const uint8_t *container = (const uint8_t *)dContainer;
   const uint8_t *payload = container + HSRLE_CONTAINER_HEADER_SIZE + 8ull * ((uint64_t)info->blockCount + 1ull);
   DecodeArgs da{ payload, (const uint64_t *)(container + HSRLE_CONTAINER_HEADER_SIZE), payload + info->payloadSize + HSRLE_CONTAINER_TAIL_PAD,
                  (uint8_t *)dOut, info->uncompressedSize, info->blockSize, first, count, dStatus };
-  return g_sub[info->codec](da, 0u, nullptr, st) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;     // (sub-block size 0 = the wave decoder)
+  return g_launch[info->codec].sub(da, 0u, nullptr, st) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;     // (sub-block size 0 = the wave decoder)
 }
 
 } // namespace hsrle

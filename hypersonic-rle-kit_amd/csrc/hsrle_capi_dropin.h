@@ -17,7 +17,7 @@ static uint32_t mono_compress(int codec, const uint8_t *pIn, uint32_t inSize, ui
     return 0;
 
   init_tables();
-  if (!g_enc[codec])
+  if (!g_launch[codec].enc)
     return 0;
 
   Staging s;
@@ -26,7 +26,7 @@ static uint32_t mono_compress(int codec, const uint8_t *pIn, uint32_t inSize, ui
     return 0;
 
   // many lanes where the codec allows it (cuts behind long runs, hsrle_mono_encode.hip.h); else -- and for inputs of one piece -- one lane
-  if (g_menc[codec])
+  if (g_launch[codec].menc)
   {
     const MonoEncPlan m = plan_mono_encode(inSize, codec);
     if (m.pieces >= 2u)
@@ -44,7 +44,7 @@ static uint32_t mono_compress(int codec, const uint8_t *pIn, uint32_t inSize, ui
   if (!s.up(pIn, inSize))
     return 0;
   EncodeArgs ea{ s.in, inSize, inSize, 1u, s.out, stride, s.status };
-  if (g_enc[codec](ea, nullptr) != hipSuccess)
+  if (g_launch[codec].enc(ea, nullptr) != hipSuccess)
     return 0;
   uint32_t size = 0;
   if (!s.words(&size, s.status, 1) || size == 0 || size > outSize || !s.down(pOut, s.out, size))

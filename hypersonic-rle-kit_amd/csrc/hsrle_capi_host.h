@@ -10,38 +10,15 @@
 
 namespace hsrle {
 
-static DecodeLaunch g_dec[kCodecCount];
-static EncodeLaunch g_enc[kCodecCount];
-static IndexLaunch g_idx[kCodecCount];
-static SubBlockLaunch g_sub[kCodecCount];
-static MonoEncodeLaunch g_menc[kCodecCount];
-static WaveEncodeLaunch g_wenc[kCodecCount];
-static PpwLaunch g_ppwL[kCodecCount];               // ... and those of hsrle_encodeLp.hip.h (hsrle_encodeLpw.hip.h)
-static PpwLaunch g_ppwS[kCodecCount];               // ... and the codecs of hsrle_encodeSp.hip.h (hsrle_encodeSpw.hip.h), by codec id
-static PpwLaunch g_ppw[kCodecCount];               // ... for units of any length (hsrle_encode8pw.hip.h), by codec id: rle8_multi, rle8_packed_multi
-static PpwLaunch g_ppwSM[kCodecCount];              // ... the chunk mode of hsrle_encodeSpw.hip.h (the chunks of one monolithic stream), by codec id: 42 codecs
-static PpLaunch g_pp[kCodecCount];                  // position-parallel encoders (hsrle_encode8p.hip.h)
+static CodecLaunch g_launch[kCodecCount];   // [codec id]: every launcher of the codec (hsrle_launch.h); zero = the codec has none of that kind
 static std::once_flag g_tableOnce;
 
 static void init_tables()
 {
   std::call_once(g_tableOnce, [] {
-    register_w8(g_dec, g_enc, g_idx, g_sub, g_menc, g_wenc);
-    register_pp8(g_pp);
-    register_pp8w(g_ppw);
-    register_ppSw(g_ppwS);
-    register_ppSwM(g_ppwSM);
-    register_ppLw(g_ppwL);
-    register_pp8s(g_pp);
-    register_pp128(g_pp);
-    register_ppL(g_pp);
-    register_ppS(g_pp);
-    register_w16(g_dec, g_enc, g_idx, g_sub, g_menc);
-    register_w24(g_dec, g_enc, g_idx, g_sub, g_menc);
-    register_w32(g_dec, g_enc, g_idx, g_sub, g_menc);
-    register_w48(g_dec, g_enc, g_idx, g_sub, g_menc);
-    register_w64(g_dec, g_enc, g_idx, g_sub, g_menc);
-    register_w128(g_dec, g_enc, g_idx, g_sub, g_menc);
+    for (auto reg : { register_w8, register_w16, register_w24, register_w32, register_w48, register_w64, register_w128, register_pp8, register_pp8s, register_pp128, register_ppL,
+                      register_ppS, register_pp8w, register_ppLw, register_ppSw })
+      reg(g_launch);
   });
 }
 

@@ -1,15 +1,12 @@
-// hsrle_mmtf_capi.hip -- C ABI of the mmtf / bitmmtf transforms (include/hsrle.h section 5; reference: src/rle.h:420-438, src/mmtf.c, src/bit_mmtf.c).
+// hsrle_capi_mmtf.h -- part of hsrle_capi.hip: C ABI of the mmtf / bitmmtf transforms (include/hsrle.h section 5; reference: src/rle.h:420-438, src/mmtf.c, src/bit_mmtf.c).
 // The plan (segment length, chunk length, workspace layout) is made here on the host from the size alone; inst_mmtf.hip launches it.
 // Behind it: the C ABI of the rle8_mmtf128 codec (reference: src/rle8_mmtf.c, src/rle.h:442-452), which runs the mmtf128 plan between its own passes
-// (kernels: hsrle_rle8mmtf.hip.h, launched by inst_rle8mmtf.hip).
-#include "../../include/hsrle.h"
-
+// (kernels: hsrle_rle8mmtf.hip.h, launched by inst_rle8mmtf.hip).  No kernel here.  The host-pointer functions stage like every other family: one Staging.
+#pragma once
+#include "hsrle_capi_host.h"
 #include "hsrle_mmtf.h"
 
-#include <atomic>
 #include <math.h>
-#include <mutex>
-#include <string.h>
 
 namespace hsrle {
 
@@ -91,42 +88,19 @@ static bool mmtf_plan(int transform, uint64_t size, MmtfPlan &p)
   return true;
 }
 
-// ---- staging of the host-pointer functions: per device, one call at a time on a device (as the other drop-in functions, hsrle_capi.hip) ----
-constexpr int kMmtfMaxDevices = 64;
-struct MmtfStaging
-{
-  std::mutex mu;
-  void *in = nullptr, *out = nullptr, *ws = nullptr;
-  uint64_t inSize = 0, outSize = 0, wsSize = 0;
-};
-static MmtfStaging g_mmtfStaging[kMmtfMaxDevices];
-
-static bool mmtf_grow(void **p, uint64_t *have, uint64_t need)
-{
-  if (*p && *have >= need) return true;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *have = 0;
-  if (hipMalloc(p, need) != hipSuccess) { (void)hipGetLastError(); return false; }
-  *have = need;
-  return true;
-}
-
+// ---- the host-pointer functions: one Staging each (hsrle_capi_host.h), so they run one after the other with every other drop-in call on the device ----
 static uint32_t mmtf_dropin(int transform, int decode, const uint8_t *pIn, uint32_t inSize, uint8_t *pOut, uint32_t outSize)
 {
   if (pIn == nullptr || pOut == nullptr || inSize == 0u || inSize > outSize)   // (mmtf.c does not look at the pointers; a NULL here is a 0, not a fault)
     return 0;
-  int n = 0, d = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return 0; }
-  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMmtfMaxDevices) d = 0;
-  MmtfStaging &S = g_mmtfStaging[d];
-  std::lock_guard<std::mutex> lock(S.mu);
   const uint64_t need = hsrle_mmtf_workspace_size(transform, inSize);
-  if (need == 0u || !mmtf_grow(&S.in, &S.inSize, (uint64_t)inSize + 64u) || !mmtf_grow(&S.out, &S.outSize, (uint64_t)inSize + 64u) || !mmtf_grow(&S.ws, &S.wsSize, need))
+  if (need == 0u || !device_ok())
     return 0;
-  if (hipMemcpy(S.in, pIn, inSize, hipMemcpyHostToDevice) != hipSuccess) return 0;
-  if (hsrle_mmtf_dev_async(transform, decode, S.in, inSize, S.out, S.ws, S.wsSize, nullptr) != HSRLE_OK) return 0;
-  if (hipMemcpy(pOut, S.out, inSize, hipMemcpyDeviceToHost) != hipSuccess) return 0;   // (synchronises the null stream)
+  Staging s;
+  if (!s.reserve(inSize, inSize) || !s.reserve_ws(need) || !s.up(pIn, inSize))
+    return 0;
+  if (hsrle_mmtf_dev_async(transform, decode, s.in, inSize, s.out, s.ws, s.wsSize, nullptr) != HSRLE_OK || !s.down(pOut, s.out, inSize))   // (the copy synchronises the null stream)
+    return 0;
   return inSize;
 }
 
@@ -156,26 +130,22 @@ static bool rle8mmtf_plan(int decode, uint64_t size, Rle8MmtfPlan &p)
 
 static uint32_t rle8mmtf_bounds(uint32_t inSize) { return inSize > kRle8MmtfMaxIn ? 0u : inSize + 8u; }   // rle8_mmtf.c:26-32
 
-// (the device words of a host-pointer call live in the first 256 bytes of the staged workspace)
+// (size and status word of a host-pointer call: Staging::status)
 static uint32_t rle8mmtf_compress_dropin(const uint8_t *pIn, uint32_t inSize, uint8_t *pOut, uint32_t outSize)
 {
   if (pIn == nullptr || pOut == nullptr || inSize == 0u || inSize > kRle8MmtfMaxIn || outSize < rle8mmtf_bounds(inSize))
     return 0;
-  int n = 0, d = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return 0; }
-  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMmtfMaxDevices) d = 0;
-  MmtfStaging &S = g_mmtfStaging[d];
-  std::lock_guard<std::mutex> lock(S.mu);
   const uint64_t need = hsrle_rle8_mmtf128_workspace_size(0, inSize);
-  if (need == 0u || !mmtf_grow(&S.in, &S.inSize, (uint64_t)inSize + 64u) || !mmtf_grow(&S.out, &S.outSize, (uint64_t)inSize + 64u) || !mmtf_grow(&S.ws, &S.wsSize, need + 256u))
+  if (need == 0u || !device_ok())
     return 0;
-  uint32_t *words = (uint32_t *)S.ws;
-  if (hipMemcpy(S.in, pIn, inSize, hipMemcpyHostToDevice) != hipSuccess) return 0;
-  if (hsrle_rle8_mmtf128_compress_dev_async(S.in, inSize, S.out, (uint64_t)inSize + 64u, words, words + 1, (uint8_t *)S.ws + 256, need, nullptr) != HSRLE_OK) return 0;
-  uint32_t h[2] = { 0u, 1u };
-  if (hipMemcpy(h, words, 8, hipMemcpyDeviceToHost) != hipSuccess) return 0;   // (synchronises the null stream)
-  if (h[1] != HSRLE_RLE8_MMTF_DONE || h[0] == 0u || h[0] > outSize) return 0;
-  if (hipMemcpy(pOut, S.out, h[0], hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  Staging s;
+  if (!s.reserve(inSize, inSize) || !s.reserve_ws(need) || !s.up(pIn, inSize))
+    return 0;
+  if (hsrle_rle8_mmtf128_compress_dev_async(s.in, inSize, s.out, (uint64_t)inSize + 64u, s.status, s.status + 1, s.ws, s.wsSize, nullptr) != HSRLE_OK)
+    return 0;
+  uint32_t h[2] = { 0u, 1u };   // size, status
+  if (!s.words(h, s.status, 2) || h[1] != HSRLE_RLE8_MMTF_DONE || h[0] == 0u || h[0] > outSize || !s.down(pOut, s.out, h[0]))
+    return 0;
   return h[0];
 }
 
@@ -188,27 +158,21 @@ static uint32_t rle8mmtf_decompress_dropin(const uint8_t *pIn, uint32_t inSize, 
   const uint32_t expectedOut = hdr[0], expectedIn = hdr[1];
   if (expectedOut > outSize || expectedIn > inSize || expectedOut == 0u || expectedOut > kRle8MmtfMaxIn || expectedIn < 8u)
     return 0;
-  int n = 0, d = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return 0; }
-  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMmtfMaxDevices) d = 0;
-  MmtfStaging &S = g_mmtfStaging[d];
-  std::lock_guard<std::mutex> lock(S.mu);
   const uint64_t need = hsrle_rle8_mmtf128_workspace_size(1, expectedOut);
-  if (need == 0u || !mmtf_grow(&S.in, &S.inSize, (uint64_t)expectedIn + 64u) || !mmtf_grow(&S.out, &S.outSize, (uint64_t)expectedOut + 64u) || !mmtf_grow(&S.ws, &S.wsSize, need + 256u))
+  if (need == 0u || !device_ok())
     return 0;
-  uint32_t *words = (uint32_t *)S.ws;
-  if (hipMemcpy(S.in, pIn, expectedIn, hipMemcpyHostToDevice) != hipSuccess) return 0;
-  if (hsrle_rle8_mmtf128_decompress_dev_async(S.in, expectedIn, S.out, expectedOut, words, (uint8_t *)S.ws + 256, need, nullptr) != HSRLE_OK) return 0;
+  Staging s;
+  if (!s.reserve(expectedIn, expectedOut) || !s.reserve_ws(need) || !s.up(pIn, expectedIn))
+    return 0;
+  if (hsrle_rle8_mmtf128_decompress_dev_async(s.in, expectedIn, s.out, expectedOut, s.status, s.ws, s.wsSize, nullptr) != HSRLE_OK)
+    return 0;
   uint32_t status = 1u;
-  if (hipMemcpy(&status, words, 4, hipMemcpyDeviceToHost) != hipSuccess) return 0;
-  if (status != HSRLE_RLE8_MMTF_DONE) return 0;
-  if (hipMemcpy(pOut, S.out, expectedOut, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  if (!s.words(&status, s.status, 1) || status != HSRLE_RLE8_MMTF_DONE || !s.down(pOut, s.out, expectedOut))
+    return 0;
   return expectedOut;
 }
 
 }   // namespace hsrle
-
-using namespace hsrle;
 
 extern "C" {
 

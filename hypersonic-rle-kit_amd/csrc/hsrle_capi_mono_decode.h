@@ -157,7 +157,7 @@ struct MonoRun
 static int mono_prepare(const MonoHeader &mh, const uint8_t *dStream, uint8_t *dOut, uint8_t *ws, const MonoPlan &m, MonoRun *run, hipStream_t st)
 {
   init_tables();
-  if (!g_dec[mh.codec] || !g_idx[mh.codec])
+  if (!g_launch[mh.codec].dec || !g_launch[mh.codec].idx)
     return HSRLE_ERR_UNSUPPORTED;
   uint32_t *ctrl = (uint32_t *)(ws + m.offCtrl);
   // mark | ctrl | records are neighbours in the workspace (plan_mono), every piece a multiple of 256 bytes: ONE clearing launch.  (Not
@@ -188,13 +188,13 @@ static int mono_prepare(const MonoHeader &mh, const uint8_t *dStream, uint8_t *d
 // walk of every region, resolve round 1, gated records, decode (unless only the index is wanted): nothing here waits for the host
 static int mono_enqueue_first_try(const MonoHeader &mh, uint8_t *ws, const MonoPlan &m, MonoRun &run, hipStream_t st, bool decode = true)
 {
-  if (g_idx[mh.codec](run.ia, 0, st) != hipSuccess || launch_resolve(m, ws, mh.p0, mh.U, 1u, st) != hipSuccess)
+  if (g_launch[mh.codec].idx(run.ia, 0, st) != hipSuccess || launch_resolve(m, ws, mh.p0, mh.U, 1u, st) != hipSuccess)
     return HSRLE_ERR_DEVICE;
   run.ia.gate = run.ctrl;
-  const hipError_t e = g_idx[mh.codec](run.ia, 1, st);
+  const hipError_t e = g_launch[mh.codec].idx(run.ia, 1, st);
   run.ia.gate = nullptr;
   run.da.gate = run.ctrl;                                                // (the decode too: nothing to decode from records that were not written)
-  const hipError_t e2 = (e != hipSuccess || !decode) ? e : g_dec[mh.codec](run.da, st);
+  const hipError_t e2 = (e != hipSuccess || !decode) ? e : g_launch[mh.codec].dec(run.da, st);
   run.da.gate = nullptr;
   if (e2 != hipSuccess)
     return HSRLE_ERR_DEVICE;
@@ -238,7 +238,7 @@ static int mono_decode_dev(const MonoHeader &mh, const uint8_t *dStream, uint8_t
     uint32_t pg[128], pe[128];
     IndexArgs pilot = ia;
     pilot.R = 128u;
-    if (g_idx[mh.codec](pilot, 0, st) != hipSuccess || hipMemcpyAsync(pg, ia.g, sizeof(pg), hipMemcpyDeviceToHost, st) != hipSuccess ||
+    if (g_launch[mh.codec].idx(pilot, 0, st) != hipSuccess || hipMemcpyAsync(pg, ia.g, sizeof(pg), hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipMemcpyAsync(pe, ia.e, sizeof(pe), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
       return HSRLE_ERR_DEVICE;
     uint32_t agree = 0;
@@ -269,7 +269,7 @@ static int mono_decode_dev(const MonoHeader &mh, const uint8_t *dStream, uint8_t
       rounds = 0;
     }
     else { ia.list = (const uint32_t *)(ws + m.offList); ia.listCount = verdict[0]; ia.roundTag = roundTag; }
-    if (g_idx[mh.codec](ia, 0, st) != hipSuccess)
+    if (g_launch[mh.codec].idx(ia, 0, st) != hipSuccess)
       return HSRLE_ERR_DEVICE;
     roundTag++;
     if (launch_resolve(m, ws, mh.p0, mh.U, roundTag, st) != hipSuccess)
@@ -286,9 +286,9 @@ static int mono_decode_dev(const MonoHeader &mh, const uint8_t *dStream, uint8_t
   // (the first try's decode lanes found zero records and left their error bits in the status word)
   ia.list = nullptr; ia.listCount = 0;
   if (!decode)
-    return g_idx[mh.codec](ia, 1, st) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
+    return g_launch[mh.codec].idx(ia, 1, st) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
   hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, st, ctrl + 8, 0u);
-  if (g_idx[mh.codec](ia, 1, st) != hipSuccess || g_dec[mh.codec](run.da, st) != hipSuccess)
+  if (g_launch[mh.codec].idx(ia, 1, st) != hipSuccess || g_launch[mh.codec].dec(run.da, st) != hipSuccess)
     return HSRLE_ERR_DEVICE;
   uint32_t status = 1;
   if (hipMemcpyAsync(&status, ctrl + 8, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)

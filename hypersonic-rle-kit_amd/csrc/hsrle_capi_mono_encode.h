@@ -22,8 +22,8 @@ struct MonoEncPlan
 };
 
 // the codecs whose encoder state at a cut is fixed by the cut itself (hsrle_codecs.h: chunk_mode): the 8 bit pair's windowed encoder, or the chunk mode of hsrle_encodeSpw.hip.h
-static PpwLaunch mono_ppw_launcher(int codec) { return !chunk_mode(kCodecs[codec]) ? nullptr : (g_ppw[codec] ? g_ppw[codec] : g_ppwSM[codec]); }
-static uint32_t mono_ppw_state_words(int codec) { return g_ppw[codec] ? kPpwStateWords : kPpwSStateWords; }
+static PpwLaunch mono_ppw_launcher(int codec) { return !chunk_mode(kCodecs[codec]) ? nullptr : (g_launch[codec].ppw8 ? g_launch[codec].ppw8 : g_launch[codec].ppwSM); }
+static uint32_t mono_ppw_state_words(int codec) { return g_launch[codec].ppw8 ? kPpwStateWords : kPpwSStateWords; }
 static bool mono_windowed(int codec) { return mono_ppw_launcher(codec) != nullptr && kPpwMinBlocks != 0xFFFFFFFFu && knob_u32("HSRLE_PP", 0u) != 2u; }
 
 static MonoEncPlan plan_mono_encode(uint32_t U, int codec, bool lists = true)
@@ -94,7 +94,7 @@ static int mono_encode_dev(int codec, const uint8_t *dIn, uint32_t U, uint8_t *d
   const CodecInfo &ci = kCodecs[codec];
   const int S = ci.S, listK = list_len(ci);
   const uint32_t longc = cut_long(ci);
-  if (!g_menc[codec])
+  if (!g_launch[codec].menc)
     return HSRLE_ERR_UNSUPPORTED;
   const bool single = is_single(ci);
   const uint32_t hs = header_size(ci) + (single ? 1u : 0u);   // (Single: the symbol byte follows the header)
@@ -176,7 +176,7 @@ static int mono_encode_dev(int codec, const uint8_t *dIn, uint32_t U, uint8_t *d
   if (single) { ma.jobs = (uint64_t *)(ws + m.offJobs); ma.jobCount = ctrl + 12; ma.jobCap = m.jobCap; }   // (ctrl[12] was zeroed with the rest)
   if (listK == 0)
   {
-    if (g_menc[codec](ea, ma, st) != hipSuccess)
+    if (g_launch[codec].menc(ea, ma, st) != hipSuccess)
       return HSRLE_ERR_DEVICE;
   }
   else
@@ -187,7 +187,7 @@ static int mono_encode_dev(int codec, const uint8_t *dIn, uint32_t U, uint8_t *d
     ma.syms = guess; ma.listOut = listOut;
     hipLaunchKernelGGL(k_mono_list_default, dim3((chunks + 255u) / 256u), dim3(256), 0, st, chunks, (uint32_t)listK, (uint32_t)S, guess);
     ma.dry = 1u;
-    if (g_menc[codec](ea, ma, st) != hipSuccess)
+    if (g_launch[codec].menc(ea, ma, st) != hipSuccess)
       return HSRLE_ERR_DEVICE;
     ma.dry = 0u;
     uint32_t rounds = 0;
@@ -213,7 +213,7 @@ static int mono_encode_dev(int codec, const uint8_t *dIn, uint32_t U, uint8_t *d
         if (todo == 0u)
           break;
       }
-      if (g_menc[codec](ea, ma, st) != hipSuccess)
+      if (g_launch[codec].menc(ea, ma, st) != hipSuccess)
         return HSRLE_ERR_DEVICE;
     }
     for (;; rounds++)
@@ -230,7 +230,7 @@ static int mono_encode_dev(int codec, const uint8_t *dIn, uint32_t U, uint8_t *d
         break;
       if (rounds > kMonoListRounds)
         return HSRLE_ERR_UNSUPPORTED;
-      if (g_menc[codec](ea, ma, st) != hipSuccess)
+      if (g_launch[codec].menc(ea, ma, st) != hipSuccess)
         return HSRLE_ERR_DEVICE;
     }
   }

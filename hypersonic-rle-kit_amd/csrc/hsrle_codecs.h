@@ -136,4 +136,34 @@ constexpr bool split_small(const CodecInfo &c) { return is_single(c) || c.S == 1
 // the 64-byte ring cost the 7-symbol LUT codecs 24 % on run-distributed data, 19 % on video-shaped; sweep of 8 GiB buffers).
 constexpr uint32_t small_ring_per_mille(const CodecInfo &c) { return c.S <= 2 ? 250u : (c.S <= 4 ? 215u : 0u); }
 
+// ---- block decode: which k_decode_blocks instantiation a launch takes.  THE rule; hsrle_launch.h: launch_decode_codec instantiates what it can return ----
+struct DecodeKnobs   // A/B builds (hsrle_launch.h: kDecodeKnobs); the shipped library has none set
+{
+  bool alwaysEnt = false;   // HSRLE_DECODE_ALWAYS_ENT: 3 .. 8 byte symbols keep the entry-record prologue (and with it the 128-byte ring) for plain containers too
+  bool pe8 = false;         // HSRLE_DEC8_PE: plain containers of rle8_multi / rle8_packed_multi go to parse + expand (csrc/experiments/hsrle_decode8pe.hip.h)
+};
+struct DecodeVariant
+{
+  Family fam;          // the kernel's FAM: Single ids decode with the multi kernels' general form, Greedy ids with the Short decoder of their grammar (the row's family)
+  bool sgl, ent, win;  // k_decode_blocks SGL / ENT / WIN
+  int ring;            // stream ring: 64, or 128 = the default one (kDecodeRing / kDec8Ring)
+  bool list8;          // an 8 bit plain / Packed kernel: tile, step and ring are kDec8Tile / kDec8Step / kDec8Ring
+  bool pe;             // not k_decode_blocks at all: k_decode8_pe<fam> (DecodeKnobs::pe8)
+};
+// window: the launch has an output window (range decode); entries: lanes start from entry records; smallRing: decode_ring_small() said yes
+constexpr DecodeVariant decode_variant(const CodecInfo &c, bool window, bool entries, bool smallRing, DecodeKnobs k = DecodeKnobs{})
+{
+  const Family fam = c.fam == SINGLE ? PLAIN : (c.fam == PACKED_SINGLE ? PACKED : c.fam);
+  const bool list8 = c.S == 1 && (fam == PLAIN || fam == PACKED);
+  const bool sgl = !(c.S == 1 && (c.fam == PLAIN || c.fam == PACKED));   // rle8_multi / rle8_packed_multi: their encoders only write mode 0
+  if (window) return { fam, sgl, true, true, 128, list8, false };
+  const bool small = !entries && smallRing && small_ring_per_mille(c) != 0u;   // (blocks decoded from entry records keep the 128-byte ring)
+  if (c.S == 1)   // one byte symbols: one instantiation with the record prologue serves both
+    return (k.pe8 && !sgl) ? DecodeVariant{ fam, sgl, true, false, 128, list8, !entries } : DecodeVariant{ fam, sgl, true, false, small ? 64 : 128, list8, false };
+  // wider symbols: plain containers take the instantiation without the entry-record prologue (same-box A/B on run-distributed data:
+  // rle32_3symlut_byte +6 %, rle48_7symlut_sym +4 %, rle64_sym +-0; the 128 bit codecs +10 %)
+  if (entries || (k.alwaysEnt && c.S >= 3 && c.S <= 8)) return { fam, true, true, false, 128, false, false };
+  return { fam, true, false, false, small ? 64 : 128, false, false };
+}
+
 } // namespace hsrle

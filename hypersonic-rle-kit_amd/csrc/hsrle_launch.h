@@ -1,4 +1,4 @@
-// hsrle_launch.h -- host-side launch table: codec id -> kernel launcher.  The kernels are instantiated per symbol
+// hsrle_launch.h -- host-side launch table: codec id -> kernel launchers (CodecLaunch).  The kernels are instantiated per symbol
 // width in inst_w*.hip (one translation unit per width so the library builds in parallel).
 #pragma once
 #include <atomic>
@@ -141,22 +141,78 @@ constexpr int kDecodeStep = HSRLE_DECODE_STEP; // output bytes per lane and deco
 constexpr int kDecodeTile = HSRLE_DECODE_TILE; // bytes produced per lane and round (k_decode_blocks T)
 constexpr int kDecodeRing = HSRLE_DECODE_RING; // per-lane stream ring in LDS (k_decode_blocks R)
 
-void register_w8(DecodeLaunch *dec, EncodeLaunch *enc, IndexLaunch *idx, SubBlockLaunch *sub, MonoEncodeLaunch *menc, WaveEncodeLaunch *wenc);
-void register_pp8(PpLaunch *pp);
-void register_pp8w(PpwLaunch *ppw);   // [codec id]: rle8_multi, rle8_packed_multi
-void register_ppLw(PpwLaunch *ppw);   // [codec id]: the codecs of hsrle_encodeLp.hip.h, blocks above 4 KiB
-void register_ppSw(PpwLaunch *ppw);   // [codec id]: the codecs of hsrle_encodeSp.hip.h, blocks above 4 KiB
-void register_ppSwM(PpwLaunch *ppw);  // [codec id]: their chunk mode (the chunks of one monolithic stream), the 42 codecs the cut fixes the state of
-void register_pp8s(PpLaunch *pp);
-void register_pp128(PpLaunch *pp);
-void register_ppL(PpLaunch *pp);
-void register_ppS(PpLaunch *pp);
-void register_w16(DecodeLaunch *dec, EncodeLaunch *enc, IndexLaunch *idx, SubBlockLaunch *sub, MonoEncodeLaunch *menc);
-void register_w24(DecodeLaunch *dec, EncodeLaunch *enc, IndexLaunch *idx, SubBlockLaunch *sub, MonoEncodeLaunch *menc);
-void register_w32(DecodeLaunch *dec, EncodeLaunch *enc, IndexLaunch *idx, SubBlockLaunch *sub, MonoEncodeLaunch *menc);
-void register_w48(DecodeLaunch *dec, EncodeLaunch *enc, IndexLaunch *idx, SubBlockLaunch *sub, MonoEncodeLaunch *menc);
-void register_w64(DecodeLaunch *dec, EncodeLaunch *enc, IndexLaunch *idx, SubBlockLaunch *sub, MonoEncodeLaunch *menc);
-void register_w128(DecodeLaunch *dec, EncodeLaunch *enc, IndexLaunch *idx, SubBlockLaunch *sub, MonoEncodeLaunch *menc);
+// the 8 bit list-free (plain / Packed) decoders' tile row, step and ring (A/B builds: -DHSRLE_DEC8_TILE=64 -DHSRLE_DEC8_STEP=64)
+#ifndef HSRLE_DEC8_TILE
+#define HSRLE_DEC8_TILE HSRLE_DECODE_TILE
+#endif
+#ifndef HSRLE_DEC8_STEP
+#define HSRLE_DEC8_STEP HSRLE_DECODE_STEP
+#endif
+#ifndef HSRLE_DEC8_RING
+#define HSRLE_DEC8_RING HSRLE_DECODE_RING
+#endif
+constexpr int kDec8Tile = HSRLE_DEC8_TILE, kDec8Step = HSRLE_DEC8_STEP, kDec8Ring = HSRLE_DEC8_RING;
+// the A/B build knobs of the decode rule (hsrle_codecs.h: decode_variant) and of the encoders of 2 .. 8 byte symbols (hsrle_inst_generic.inc)
+#ifdef HSRLE_DECODE_ALWAYS_ENT
+constexpr bool kDecodeAlwaysEnt = true;
+#else
+constexpr bool kDecodeAlwaysEnt = false;
+#endif
+#ifdef HSRLE_DEC8_PE
+constexpr bool kDec8Pe = true;
+#else
+constexpr bool kDec8Pe = false;
+#endif
+constexpr DecodeKnobs kDecodeKnobs{ kDecodeAlwaysEnt, kDec8Pe };
+#ifdef HSRLE_ENCODE_V1   // the first-generation encoder (per-lane global reads and writes, hsrle_encode.hip.h)
+constexpr bool kEncodeV1 = true;
+#else
+constexpr bool kEncodeV1 = false;
+#endif
+#ifdef HSRLE_ENCS_RING   // one history ring for every width (hsrle_encodeS.hip.h)
+constexpr bool kEncSRingFixed = true;
+#else
+constexpr bool kEncSRingFixed = false;
+#endif
+
+// One row per codec id: every launcher the codec has (nullptr: none).  The inst_*.hip units fill their columns (register_*), hsrle_capi_host.h owns the table.
+struct CodecLaunch
+{
+  DecodeLaunch dec; EncodeLaunch enc; IndexLaunch idx; SubBlockLaunch sub; MonoEncodeLaunch menc;
+  WaveEncodeLaunch wenc;   // experiment builds: rle8_multi, rle8_packed_multi
+  PpLaunch pp;             // position-parallel encoder, blocks up to 4 KiB
+  // the windowed position-parallel encoders, blocks above 4 KiB: rle8_multi / rle8_packed_multi (hsrle_encode8pw.hip.h, also the chunks of their monolithic streams),
+  // the codecs of hsrle_encodeLp.hip.h, those of hsrle_encodeSp.hip.h -- and the latter's chunk mode (the chunks of one monolithic stream): the 42 codecs the cut fixes the state of
+  PpwLaunch ppw8, ppwL, ppwS, ppwSM;
+};
+void register_w8(CodecLaunch *t);
+void register_w16(CodecLaunch *t);
+void register_w24(CodecLaunch *t);
+void register_w32(CodecLaunch *t);
+void register_w48(CodecLaunch *t);
+void register_w64(CodecLaunch *t);
+void register_w128(CodecLaunch *t);
+void register_pp8(CodecLaunch *t);
+void register_pp8s(CodecLaunch *t);
+void register_pp128(CodecLaunch *t);
+void register_ppL(CodecLaunch *t);
+void register_ppS(CodecLaunch *t);
+void register_pp8w(CodecLaunch *t);
+void register_ppLw(CodecLaunch *t);
+void register_ppSw(CodecLaunch *t);    // ppwS and ppwSM
+
+// the scratch of a position-parallel launch as its kernels take it (PpScratch: hsrle_encode8p.hip.h)
+struct PpScratch;
+template <typename SCRATCH = PpScratch>
+inline SCRATCH pp_scratch_of(const PpArgs &a)
+{
+  SCRATCH sc;
+  sc.recs = (uint32_t *)a.scratch;
+  sc.recStride = pp_record_stride(a.B);
+  sc.recCount = sc.recs + (uint64_t)sc.recStride * a.nBlocks + 64u;   // (+ 64: the last block's lanes read 64 words from its first record on)
+  sc.stamps = nullptr;
+  return sc;
+}
 
 template <typename... A>
 constexpr int kernel_arity(void (*)(A...)) { return (int)sizeof...(A); }
@@ -179,7 +235,7 @@ inline hipError_t launch_decode(KERNEL k, const DecodeArgs &a, hipStream_t st)
 // does finishes in the second pass).  8 GiB video-shaped rle8_packed (ratio 0.18): 3.90 -> 3.34 ms; at ratio 0.43 it would lose 9 %,
 // on run-distributed data 9 - 25 %.  Blocks decoded from entry records (monolithic streams, split decode) keep the 128-byte ring.
 // HSRLE_DEC_RING=64 / 128 in the environment forces one (tests, A/B; experiment builds).
-// THE predicate: launch_decode_ring below and hsrle_decode_ring (include/hsrle.h) both ask it, with the codec's threshold from its row (hsrle_codecs.h:
+// THE predicate: launch_decode_codec below and hsrle_decode_ring (include/hsrle.h) both ask it, with the codec's threshold from its row (hsrle_codecs.h:
 // small_ring_per_mille; a codec without a 64-byte instantiation never takes one, forced or not).  readableBytes = payloadSize + the tail pad.
 inline bool decode_ring_small(const CodecInfo &c, uint64_t U, uint64_t readableBytes)
 {
@@ -188,14 +244,40 @@ inline bool decode_ring_small(const CodecInfo &c, uint64_t U, uint64_t readableB
   if (perMille == 0u) return false;
   return forced ? forced == 64 : readableBytes * 1000u < U * perMille;
 }
-// CODEC: the id of a codec this decoder serves (ids that share a decoder share the symbol width, and with it the threshold).  A query
-// (a.residentWorkgroups) has U == 0 and gets the 128-byte instantiation unless one is forced.
-template <int CODEC, typename K128, typename K64>
-inline hipError_t launch_decode_ring(K128 k128, K64 k64, const DecodeArgs &a, hipStream_t st)
+// The block decoder (hsrle_decode.hip.h; declared here so that the launcher below stands in a header the C-ABI unit reads too)
+template <int FAM, int S, int AL, int T, int R, int Q, bool SGL, bool ENT, bool WIN>
+__global__ void k_decode_blocks(const uint8_t *__restrict__ payload, const uint64_t *__restrict__ offsets, const uint8_t *__restrict__ payloadEnd, uint8_t *__restrict__ out, uint64_t U,
+                                uint32_t B, uint32_t firstBlock, uint32_t blockCount, uint32_t *__restrict__ status, const uint32_t *__restrict__ entries, uint32_t entryBase,
+                                const uint32_t *__restrict__ gate, uint32_t gateWords, uint64_t winLo, uint64_t winHi);
+#ifdef HSRLE_DEC8_PE   // ... and the experiment's (csrc/experiments/hsrle_decode8pe.hip.h)
+template <int FAM>
+__global__ void k_decode8_pe(const uint8_t *__restrict__ payload, const uint64_t *__restrict__ offsets, const uint8_t *__restrict__ payloadEnd, uint8_t *__restrict__ out, uint64_t U,
+                             uint32_t B, uint32_t firstBlock, uint32_t blockCount, uint32_t *__restrict__ status, const uint32_t *__restrict__ entries, uint32_t entryBase,
+                             const uint32_t *__restrict__ gate, uint32_t gateWords, uint64_t winLo, uint64_t winHi);
+#endif
+
+// one case of the rule (hsrle_codecs.h: decode_variant) for codec id C: the kernel it names.  Cases with the same answer are the same kernel.
+template <int C, bool WINDOW, bool ENTRIES, bool SMALL>
+inline hipError_t launch_decode_case(const DecodeArgs &a, hipStream_t st)
 {
-  static_assert(small_ring_per_mille(kCodecs[CODEC]) != 0u, "a 64-byte ring instantiation for a codec whose row says it never takes one");
-  if (a.entries == nullptr && decode_ring_small(kCodecs[CODEC], a.U, (uint64_t)(a.payloadEnd - a.payload))) return launch_decode(k64, a, st);
-  return launch_decode(k128, a, st);
+  constexpr DecodeVariant v = decode_variant(kCodecs[C], WINDOW, ENTRIES, SMALL, kDecodeKnobs);
+  constexpr int S = kCodecs[C].S, AL = kCodecs[C].aligned, T = v.list8 ? kDec8Tile : kDecodeTile, Q = v.list8 ? kDec8Step : kDecodeStep;
+  constexpr int R = v.ring == 64 ? 64 : (v.list8 ? kDec8Ring : kDecodeRing);
+#ifdef HSRLE_DEC8_PE
+  if constexpr (v.pe) return launch_decode(k_decode8_pe<v.fam>, a, st);
+  else
+#endif
+  return launch_decode(k_decode_blocks<v.fam, S, AL, T, R, Q, v.sgl, v.ent, v.win>, a, st);
+}
+// THE decode launcher of codec id C: instantiates what the rule can answer for this codec and takes the one it answers for this launch.  A query
+// (a.residentWorkgroups) has U == 0 and no entries: it gets the plain container's 128-byte instantiation unless a ring is forced.
+template <int C>
+inline hipError_t launch_decode_codec(const DecodeArgs &a, hipStream_t st)
+{
+  if (windowed(a)) return launch_decode_case<C, true, false, false>(a, st);
+  if (a.entries != nullptr) return launch_decode_case<C, false, true, false>(a, st);
+  if (decode_ring_small(kCodecs[C], a.U, (uint64_t)(a.payloadEnd - a.payload))) return launch_decode_case<C, false, false, true>(a, st);
+  return launch_decode_case<C, false, false, false>(a, st);
 }
 
 // rle8_multi / rle8_packed_multi: which containers the run list encoder takes (hsrle_encode8r.hip.h; force: 1 always, 2 never -- experiment builds)

@@ -1,4 +1,4 @@
-// hsrle_mmtf.h -- host side of the mmtf / bitmmtf transforms: what hsrle_mmtf_capi.hip plans and inst_mmtf.hip launches (kernels: hsrle_mmtf.hip.h).
+// hsrle_mmtf.h -- host side of the mmtf / bitmmtf transforms: what hsrle_capi_mmtf.h (a part of hsrle_capi.hip) plans and inst_mmtf.hip launches (kernels: hsrle_mmtf.hip.h).
 #pragma once
 
 #include <hip/hip_runtime.h>

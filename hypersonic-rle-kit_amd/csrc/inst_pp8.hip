@@ -7,10 +7,7 @@ namespace hsrle {
 template <int FAM>
 static hipError_t pp_launch(const PpArgs &a, int phase, hipStream_t st)
 {
-  PpScratch sc;
-  sc.recs = (uint32_t *)a.scratch;
-  sc.recStride = pp_record_stride(a.B);
-  sc.recCount = sc.recs + (uint64_t)sc.recStride * a.nBlocks + 64u;   // (+ 64: the last block's lanes read 64 words from its first record on)
+  PpScratch sc = pp_scratch_of(a);
   sc.stamps = a.scratch + ((pp_scratch_bytes(a.nBlocks, a.B) + 255ull) & ~255ull);   // (diagnostic builds: 128 bytes per block behind the scratch, in the caller's slot area)
   if (phase == 0)
     hipLaunchKernelGGL((k_encode8_pp<FAM, 0>), dim3((a.nBlocks + kPp8Bpw - 1u) / kPp8Bpw), dim3(64), 0, st, a.in, a.U, a.B, a.nBlocks, a.sizes, a.offsets, a.payload, sc);
@@ -19,10 +16,10 @@ static hipError_t pp_launch(const PpArgs &a, int phase, hipStream_t st)
   return hipGetLastError();
 }
 
-void register_pp8(PpLaunch *pp)
+void register_pp8(CodecLaunch *t)
 {
-  pp[codec_id(PLAIN, 1, 0)] = pp_launch<PLAIN>;
-  pp[codec_id(PACKED, 1, 0)] = pp_launch<PACKED>;
+  t[codec_id(PLAIN, 1, 0)].pp = pp_launch<PLAIN>;
+  t[codec_id(PACKED, 1, 0)].pp = pp_launch<PACKED>;
 }
 
 } // namespace hsrle

@@ -15,10 +15,10 @@ static hipError_t ppw_launch(const PpwArgs &a, int phase, hipStream_t st)
   return hipGetLastError();
 }
 
-void register_pp8w(PpwLaunch *ppw)
+void register_pp8w(CodecLaunch *t)
 {
-  ppw[codec_id(PLAIN, 1, 0)] = ppw_launch<PLAIN>;
-  ppw[codec_id(PACKED, 1, 0)] = ppw_launch<PACKED>;
+  t[codec_id(PLAIN, 1, 0)].ppw8 = ppw_launch<PLAIN>;
+  t[codec_id(PACKED, 1, 0)].ppw8 = ppw_launch<PACKED>;
 }
 
 } // namespace hsrle

@@ -1,6 +1,7 @@
 """csrc/hsrle_codecs.h against an independent table: a small host program (plain g++, no HIP) prints every row of kCodecs and what the accessors derive from
 it; name, family, symbol bytes and alignment must be those of hsrle_testlib.CODECS (built from the reference's naming scheme, not from the header), the list
-length the one the name states, codec_id() the inverse of the table, and the stream header 9 bytes for the four 8 bit plain / Packed codecs and 8 elsewhere."""
+length the one the name states, codec_id() the inverse of the table, and the stream header 9 bytes for the four 8 bit plain / Packed codecs and 8 elsewhere.
+The decode rule (decode_variant: which k_decode_blocks instantiation a launch takes) is printed for every row and case and compared with the rule written out here."""
 import os
 import re
 import subprocess
@@ -23,6 +24,11 @@ int main()
     const CodecInfo &i = kCodecs[c];
     printf("%%d %%s %%d %%d %%d %%d %%d %%d %%u %%u %%d %%u\n", c, i.name, (int)i.fam, (int)i.S, (int)i.aligned, (int)i.greedy, list_len(i), state_slots(i), header_size(i), cut_long(i),
            codec_id(i.fam, i.S, i.aligned, i.greedy), small_ring_per_mille(i));
+    for (int k = 0; k < 8; k++)   // bit 2: output window, bit 1: entry records, bit 0: the small-ring predicate said yes
+    {
+      const DecodeVariant v = decode_variant(i, (k & 4) != 0, (k & 2) != 0, (k & 1) != 0);
+      printf("variant %%d %%d %%d %%d %%d %%d %%d %%d %%d\n", c, k, (int)v.fam, (int)v.sgl, (int)v.ent, (int)v.win, v.ring, (int)v.list8, (int)v.pe);
+    }
   }
   return 0;
 }
@@ -41,7 +47,15 @@ def rows(tmp_path_factory):
     subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", str(src), "-o", str(exe)])
     out = subprocess.check_output([str(exe)], text=True)
     keys = ("id", "name", "fam", "S", "aligned", "greedy", "K", "slots", "header", "cut", "found", "ring")
-    return [{k: (v if k == "name" else int(v)) for k, v in zip(keys, line.split())} for line in out.splitlines()]
+    table = [{k: (v if k == "name" else int(v)) for k, v in zip(keys, line.split())} for line in out.splitlines() if not line.startswith("variant")]
+    for r in table:
+        r["variants"] = {}
+    vkeys = ("fam", "sgl", "ent", "win", "ring", "list8", "pe")
+    for line in out.splitlines():
+        if line.startswith("variant"):
+            c, k, *v = [int(x) for x in line.split()[1:]]
+            table[c]["variants"][k] = dict(zip(vkeys, v))
+    return table
 
 
 def test_one_row_per_codec_in_id_order(rows):
@@ -80,3 +94,82 @@ def test_small_ring_threshold_goes_by_the_symbol_width(rows):
     """The decoder's 64-byte stream ring: below a quarter for 1 / 2 byte symbols, below 0.215 for 3 / 4 byte symbols, never for wider ones."""
     for r in rows:
         assert r["ring"] == (250 if r["S"] <= 2 else 215 if r["S"] <= 4 else 0), r["name"]
+
+
+# ---- the decode rule: every row x (output window, entry records, small-ring predicate) ----
+PLAIN_, PACKED_, SINGLE_, PACKED_SINGLE_ = 0, 1, 4, 5
+
+
+def _expected_variant(r, window, entries, small):
+    """The table of DESIGN.md 4.1 (first case that applies), from the row's name, family number and symbol bytes alone."""
+    fam = {SINGLE_: PLAIN_, PACKED_SINGLE_: PACKED_}.get(r["fam"], r["fam"])      # Single ids decode with the multi kernels; a Greedy row's family IS its Short decoder
+    sgl = 0 if r["id"] in (0, 1) else 1
+    list8 = 1 if r["S"] == 1 and fam in (PLAIN_, PACKED_) else 0
+    if window:
+        ent, win, ring = 1, 1, 128
+    elif r["S"] == 1:
+        ent, win, ring = 1, 0, 64 if (not entries and small) else 128
+    elif entries:
+        sgl, ent, win, ring = 1, 1, 0, 128
+    else:
+        sgl, ent, win, ring = 1, 0, 0, 64 if (small and r["S"] <= 4) else 128
+    return {"fam": fam, "sgl": sgl, "ent": ent, "win": win, "ring": ring, "list8": list8, "pe": 0}
+
+
+def _cases(rows):
+    for r in rows:
+        assert sorted(r["variants"]) == list(range(8)), r["name"]
+        for k, v in r["variants"].items():
+            yield r, bool(k & 4), bool(k & 2), bool(k & 1), v
+
+
+def test_decode_rule_is_the_table(rows):
+    n = 0
+    for r, window, entries, small, v in _cases(rows):
+        assert v == _expected_variant(r, window, entries, small), (r["name"], window, entries, small)
+        n += 1
+    assert n == 110 * 8                                                  # the four cases of the table, each with the ring predicate false and true
+
+
+def test_decode_rule_properties(rows):
+    no_sgl, ring64, no_ent = set(), set(), set()
+    for r, window, entries, small, v in _cases(rows):
+        if not v["sgl"]:
+            no_sgl.add(r["id"])
+        if v["ring"] == 64:
+            ring64.add(r["id"])
+            assert not window and not entries and small, r["name"]      # only a plain container the predicate chose
+        else:
+            assert v["ring"] == 128
+        if not v["ent"]:
+            no_ent.add(r["id"])
+            assert r["S"] >= 2 and not window and not entries, r["name"]
+        elif r["S"] >= 2:
+            assert window or entries, r["name"]                          # ENT = 0 EXACTLY for the plain containers of 2 byte symbols and wider
+        if v["win"]:
+            assert window and v["ent"] and v["ring"] == 128, r["name"]
+        else:
+            assert not window
+        assert not v["pe"]                                               # (an experiment build's knob; none is set here)
+        assert v["list8"] == (1 if r["S"] == 1 and v["fam"] in (PLAIN_, PACKED_) else 0), r["name"]
+    assert no_sgl == {0, 1}                                              # rle8_multi, rle8_packed_multi -- in their WIN kernel too
+    assert all(not v["sgl"] for r, *_, v in _cases(rows) if r["id"] in (0, 1))
+    assert ring64 == {r["id"] for r in rows if r["S"] <= 4}
+    assert no_ent == {r["id"] for r in rows if r["S"] >= 2}
+
+
+def test_decode_family_of_single_and_greedy_ids(rows):
+    by_name = {r["name"]: r for r in rows}
+    for r in rows:
+        fams = {v["fam"] for v in r["variants"].values()}
+        assert len(fams) == 1, r["name"]                                 # one grammar per codec, whatever the launch
+        fam = fams.pop()
+        if r["name"] == "rle8_single":
+            assert fam == PLAIN_
+        elif r["name"] == "rle8_packed_single":
+            assert fam == PACKED_
+        elif r["greedy"]:
+            short = by_name[r["name"][: -len("_greedy")]]
+            assert not short["greedy"] and fam == short["fam"] and r["variants"] == short["variants"], r["name"]
+        else:
+            assert fam == r["fam"], r["name"]
