@@ -142,6 +142,22 @@ struct DecodeKnobs   // A/B builds (hsrle_launch.h: kDecodeKnobs); the shipped l
   bool alwaysEnt = false;   // HSRLE_DECODE_ALWAYS_ENT: 3 .. 8 byte symbols keep the entry-record prologue (and with it the 128-byte ring) for plain containers too
   bool pe8 = false;         // HSRLE_DEC8_PE: plain containers of rle8_multi / rle8_packed_multi go to parse + expand (csrc/experiments/hsrle_decode8pe.hip.h)
 };
+// The order of the three sections of a trip of the 8 bit packet loop (hsrle_decode.hip.h, `S == 1`): false = header, literals, run (H L R); true = literals, run,
+// header (L R H: no header section in the first trip of a pass -- a lane parses at the end of the trip that finished its packet).  Part of the rule: the kernel
+// asks with its family and SGL.  Same-box A/B per row (profiles/r11_decode_loop_order.md, 2 GiB, run-distributed / video-shaped): the list kernels gain with L R H
+// (rle8_3symlut +3.7 / +1.9 %, rle8_7symlut +6.0 / +2.4 %, rle8_3symlut_short +4.2 / +4.3 %, rle8_7symlut_short +3.8 / +5.0 %) and so does the Packed multi kernel
+// (the headline: -1.3 % time; at 2 GiB -0.1 / +0.9 %); the plain multi kernel (rle8_multi +0.6 / -1.1 %) and the kernels of the Single ids (rle8_packed_single
+// 0 / -0.9 %) lose on video-shaped data more than the spread between two batches of one library, and with them every kernel that was not measured keeps H L R.
+// A/B builds: -DHSRLE_DEC8_LRH=0 / 1 forces one order on every 8 bit kernel.
+constexpr bool dec8_loop_lrh(Family fam, bool sgl)
+{
+#ifdef HSRLE_DEC8_LRH
+  return HSRLE_DEC8_LRH != 0;
+#else
+  return fam == LUT3 || fam == LUT7 || fam == SHORT3 || fam == SHORT7 || (fam == PACKED && !sgl);
+#endif
+}
+
 struct DecodeVariant
 {
   Family fam;          // the kernel's FAM: Single ids decode with the multi kernels' general form, Greedy ids with the Short decoder of their grammar (the row's family)

@@ -601,8 +601,12 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
 #ifdef HSRLE_STAMPS
   unsigned long long tIssue = 0, tDecode = 0, tFlush = 0, tLand = 0, nRounds = 0, nIter = 0, t0, t1;
 #define HS_STAMP(acc) { t1 = __builtin_readcyclecounter(); acc += t1 - t0; t0 = t1; }
+  // how often the wave executes each section of the 8 bit packet loop: the first lane that is inside the section counts it, the lanes are summed at the end
+  uint32_t nSecH = 0, nSecL = 0, nSecR = 0;
+#define HS_SECTION(n) { if ((uint32_t)__ffsll((long long)__ballot(true)) - 1u == lane) n++; }
 #else
 #define HS_STAMP(acc)
+#define HS_SECTION(n)
 #endif
 
   // full-row flush (at the flush below): the lane's loop-invariant tile address and output offset.  The offset is a 32-bit one beside a scalar row
@@ -659,16 +663,40 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
       // a header may be parsed at sp iff sp <= spOK: MAXHDR bytes resident (or the stream completely loaded) and >= 2 bytes left
       const uint32_t spOK = umin((avail0 < lim) ? avail0 - MAXHDR : 0xFFFFFFFFu, slen - 2u);
 
+      // The loop body is three sections, each run by the wave as soon as one of its lanes needs it: H parses the next packet's header (only a lane with
+      // lit == run == 0 does), L copies literals, R fills the run.  Their order inside a trip is dec8_loop_lrh()'s choice (hsrle_codecs.h, the decode rule):
+      //   H L R  every trip begins with H.  A step ends at an output boundary, not at a packet boundary, so nearly every lane enters a step in the middle of a
+      //          packet and needs no header in its first trip -- but one lane of 64 that does makes the wave execute the section (0.65 of the steps).
+      //   L R H  the sequence H L R H L R ... without its first H: the first trip of a pass is L R, and a lane parses the NEXT header behind the R that finished
+      //          its packet.  Written as "no H in the first trip": one copy of every section, the trip's top (act, the wave's exit, the trip cap) stays in
+      //          front of H, and H's `act` is the one taken after the L and R in front of it.  (Measured forms that lost: the sections as lambdas called in
+      //          either order, +2.7 % time in EITHER order; `act` carried from trip to trip, +2.3 %; the exit test between H and L, +1.3 %.  LAB_NOTEBOOK.md 14.)
+      // The same headers are parsed from the same bytes and the same chunks go to the same tile positions; only the trip in which a lane parses moves
+      // (tools/decode_trip_model.py and the stamp build count the same saving: 0.6 H sections per step).  What holds in either order, and why:
+      //  * act: F_DONE / F_STALL clear and o < target, taken at the top of every trip -- with L R H that is behind the L and R that moved o: a lane that reached
+      //    `target` does not parse.  No header is read for a step the lane produces no bytes in, and the terminator behind the last packet is never read once
+      //    o == blen (target <= blen).  The flags are asked again in front of L / R.  A lane that stalls in L (literals not resident: `starved`) keeps lit != 0,
+      //    which alone keeps it out of R, and its F_STALL keeps it out of the next H.  A lane that stalls in H (sp > spOK) is inactive from there on.
+      //  * F_LAST: (lit | run) == 0 with F_LAST set becomes F_DONE in H, for a lane that is still short of target (it then ends with o != blen: DEC_ERR_STREAM
+      //    below).  The error bits are H's own and do not depend on the order.
+      //  * the bound: a trip of an active lane produces output bytes (L: n >= 1, or the lane stalls; R: m >= 1), consumes a header (>= 2 stream bytes) or
+      //    deactivates the lane (done / stall); a parsed packet has lit | run != 0 or sets F_DONE.  The one trip in which an active lane may do nothing is the
+      //    first of a pass under L R H (a lane that enters with lit == run == 0: the first step of a block, a lane that stalled on a header); its second trip
+      //    parses.  The loop is bounded by the resident stream bytes plus the step's output plus one.
+      //  * pass 1: spOK, avail0, `starved` and firstTrip are per pass and F_STALL is cleared with `fl` above; a stalled lane re-enters at L (lit != 0) or at H.
+      //  * capped rounds (CAP = 8): tripsLeft counts trips in either order.  roundsLeft: a round gives every lane that is neither starved nor stalled at least one
+      //    output byte -- any CAP >= 2 covers the empty first trip and the trip behind it, which parses and then runs L / R.
+      constexpr bool LRH = dec8_loop_lrh((Family)FAM, SGL);
+      [[maybe_unused]] bool firstTrip = true;                            // (L R H only; wave-uniform)
       for (;;)
       {
         const bool act = (fl & (F_DONE | F_STALL)) == 0u && o < target;
         if (__ballot(act) == 0ull) break;
         if constexpr (CAP != 0u) { if (tripsLeft-- == 0u) break; }
-        // every trip of an active lane either consumes stream bytes (a header is >= 2 bytes), produces output bytes, or
-        // deactivates the lane (done / stall), so the loop is bounded by the resident stream bytes plus the step's output
 
-        if (act && (lit | run) == 0u)
+        if (act && (LRH ? !firstTrip : true) && (lit | run) == 0u)
         {
+          HS_SECTION(nSecH)
           if ((fl & F_LAST) != 0u || sp > spOK)
           {
             // rare: end of the stream, header not resident yet, or a truncated stream
@@ -826,11 +854,14 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
           }
         }
 
+        if constexpr (LRH) firstTrip = false;
+
         if (act && (fl & (F_DONE | F_STALL)) == 0u)
         {
           // ---- literals: tile chunks at the aligned positions A + 16k receive ring bytes [sp - c + 16k, +16) ----
           if (lit != 0u)
           {
+            HS_SECTION(nSecL)
             const uint32_t resident = (avail0 > sp) ? avail0 - sp : 0u;
             const uint32_t n = umin(umin(lit, target - o), resident);
             if (n == 0u) { fl |= F_STALL; starved = true; }                // literals not resident yet: continue next pass
@@ -862,6 +893,7 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
           // ---- run: the same aligned chunks filled with the byte-broadcast symbol ----
           if (lit == 0u && run != 0u && o < target)
           {
+            HS_SECTION(nSecR)
             const uint32_t m = umin(run, target - o);
             const uint32_t q = HS_ROWPOS(o), c = q & 15u;
             const uint32_t d0 = q & ~15u;
@@ -1512,8 +1544,14 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
   {
     unsigned long long *dbg = (unsigned long long *)(status + 16);
     const unsigned long long iters = __builtin_amdgcn_readfirstlane((uint32_t)nIter);
+    // section counts of the 8 bit loop: summed over the wave, then added to one of 32 slots (slot = workgroup modulo 32, three words each from word 20 on;
+    // the caller's status buffer holds 256 dwords) -- every wave adding to ONE address is what made stamps lie before (LAB_NOTEBOOK.md)
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { nSecH += (uint32_t)__shfl_xor((int)nSecH, d, 64); nSecL += (uint32_t)__shfl_xor((int)nSecL, d, 64); nSecR += (uint32_t)__shfl_xor((int)nSecR, d, 64); }
     if (lane == 0)
     {
+      unsigned long long *const sec = dbg + 20 + (blockIdx.x & 31u) * 3u;
+      atomicAdd(sec + 0, (unsigned long long)nSecH); atomicAdd(sec + 1, (unsigned long long)nSecL); atomicAdd(sec + 2, (unsigned long long)nSecR);
       atomicAdd(dbg + 0, tIssue); atomicAdd(dbg + 1, tDecode); atomicAdd(dbg + 2, tFlush); atomicAdd(dbg + 3, tLand);
       atomicAdd(dbg + 4, nRounds); atomicAdd(dbg + 5, iters); atomicAdd(dbg + 6, 1ull);
       atomicAdd(dbg + 12, tx0); atomicAdd(dbg + 13, tx1); atomicAdd(dbg + 14, tx2); atomicAdd(dbg + 15, tx3); atomicAdd(dbg + 16, tx4);

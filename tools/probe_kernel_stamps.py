@@ -23,4 +23,7 @@ print('waves',nW,'rounds/wave',nR/nW,'iters/round',nIt/nR)
 print('cycles per round: issue %.0f decode %.0f flush %.0f land %.0f total %.0f'%(tI/nR,tD/nR,tF/nR,tL/nR,tot/nR))
 if len(d)>11 and d[11]:
     print('wave-level iterations/round %.2f ; per lane-iteration cycles: parse %.0f lit %.0f run %.0f (lane-iterations %d)'%(d[7]/nR, d[8]/d[11], d[9]/d[11], d[10]/d[11], d[11]))
+# the 8 bit packet loop's sections (32 slots of three counters from word 20 on; one step per round): the kernel's side of tools/decode_trip_model.py
+sec=d[20:116]
+if sum(sec): print('8 bit loop, sections executed per wave and step: H %.2f L %.2f R %.2f'%tuple(sum(sec[k::3])/nR for k in range(3)))
 print('ok', int(st[0].item())==0 and torch.equal(out,src))
