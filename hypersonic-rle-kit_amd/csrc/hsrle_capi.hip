@@ -103,12 +103,9 @@ int hsrle_experiments_enabled(void) { return kExperiments ? 1 : 0; }
 int hsrle_encode_path(int codec, uint64_t uncompressedSize, uint32_t blockSize)
 {
   if (codec < 0 || codec >= kCodecCount || uncompressedSize == 0 || !valid_block_size(blockSize)) return -1;
-  const Workspace w = plan_workspace(uncompressedSize, blockSize);
-  init_tables();
-  if (w.nChunks <= 1 && (pp_applies(codec, (uint32_t)w.nBlocks, blockSize) || ppw_applies(codec, (uint32_t)w.nBlocks, blockSize))) return HSRLE_PATH_POSITION_PARALLEL;
-  if (w.nChunks <= 1 && w.spSlots != 0 && split_encode_applies(codec, w.nBlocks, blockSize)) return HSRLE_PATH_SPLIT;
-  if (w.nChunks <= 1 && run_list_codec(codec) && run_list_applies(w.nBlocks, blockSize, uncompressedSize, knob_u32("HSRLE_RUNLIST", 0u))) return HSRLE_PATH_RUN_LIST;
-  return HSRLE_PATH_RING;
+  const EncodeChoice ec = encode_choice_of(codec, uncompressedSize, blockSize, encode_knobs().generic);   // (the workspace every caller has: include/hsrle.h)
+  if (ec.path == ENC_PP || ec.path == ENC_PPW) return HSRLE_PATH_POSITION_PARALLEL;
+  return ec.path == ENC_SPLIT ? HSRLE_PATH_SPLIT : (ec.runList ? HSRLE_PATH_RUN_LIST : HSRLE_PATH_RING);
 }
 
 int hsrle_decode_ring(int codec, uint64_t uncompressedSize, uint64_t payloadSize)
@@ -329,11 +326,9 @@ uint64_t hsrle_compress_workspace_size_codec(int codec, uint64_t inSize, uint32_
 {
   if (blockSize == 0) blockSize = HSRLE_DEFAULT_BLOCK_SIZE;
   if (!valid_block_size(blockSize) || inSize == 0 || codec < 0 || codec >= kCodecCount) return 0;
-  init_tables();
-  // (round 6: 8 bit Single and 128 bit containers of <= 4 KiB blocks are position-parallel -- no split regions; rle8_single_short and the Greedy codecs with a one-symbol list still take them)
-  const bool split = split_small(kCodecs[codec]) && blockSize <= 4096u && !pp_applies(codec, (uint32_t)block_count(inSize, blockSize), blockSize);
-  // (... and the windowed encoders take blocks above 4 KiB without the split regions: 1.05 x the input instead of 3.4 x)
-  return plan_workspace(inSize, blockSize, split, block_count(inSize, blockSize) <= 0xFFFFFFF0ull && ppw_applies(codec, (uint32_t)block_count(inSize, blockSize), blockSize)).total;
+  // what the path of a workspace with every region needs: the small-block regions only where the split encode takes the container (the Greedy codecs with a
+  // one-symbol list; round 6 made 8 bit Single and 128 bit position-parallel there), none where the windowed encoders do (1.05 x the input instead of 3.4 x)
+  return plan_workspace(inSize, blockSize, encode_choice_of(codec, inSize, blockSize, SPLIT_ALL).regions).total;
 }
 
 int hsrle_compress_dev_async(int codec, const void *dIn, uint64_t inSize, void *dOut, uint64_t outCapacity, uint32_t blockSize, void *dWorkspace,

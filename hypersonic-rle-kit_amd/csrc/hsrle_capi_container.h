@@ -1,4 +1,4 @@
-// hsrle_capi_container.h -- part of hsrle_capi.hip: workspace plan, encode paths and their predicates, the cut finders' launcher, block / split / wave decode
+// hsrle_capi_container.h -- part of hsrle_capi.hip: workspace plan, the encode rule's host side and the encode paths, the cut finders' launcher, the decode prologue, block / split / wave decode
 #pragma once
 #include "hsrle_capi_kernels.h"
 #include "hsrle_expand.hip.h"
@@ -12,26 +12,42 @@ namespace hsrle { constexpr uint64_t kTicketBytes = 256; }   // (scratch behind 
 namespace hsrle {
 
 // workspace layout: [slots][sizes u32][level-1 sums u64][level-2 sums u64][level-3 sums u64]
-//
-// Optionally (encode_chunk_blocks) inputs are compressed CHUNK by chunk: the compaction of chunk k (bandwidth bound, no LDS) runs on a
+// Optionally (EncodeKnobs::chunkBlocks) inputs are compressed CHUNK by chunk: the compaction of chunk k (bandwidth bound, no LDS) runs on a
 // second stream while the encode kernel (latency bound, LDS limited to 9 waves per CU) works on chunk k + 1, and the staging slots are
 // two chunks' worth instead of the whole input's (8 GiB: 2.3 GB instead of 9 GB).  The scan of a chunk's stream sizes starts at the
-// running total the previous chunk left in the offset table.
-static uint32_t encode_chunk_blocks()
+// running total the previous chunk left in the offset table.  OFF by default: measured on the 8 GiB headline buffer the overlap does not pay -- 1 130 GiB/s in one piece against 846 / 964 / 1 015 /
+// 1 063 GiB/s with chunks of 131 072 / 262 144 / 524 288 / 1 048 576 blocks (the compaction's traffic slows the encode kernel by more
+// than its own 1.8 ms, and every chunk boundary drains the GPU).  HSRLE_ENCODE_CHUNK_BLOCKS=n turns it on for callers that would rather
+// have the smaller workspace (two chunks of staging slots instead of the whole input's).
+// Windowed encoders: containers of blocks above 4 KiB whatever their size -- 8 MiB of 8 KiB / 64 KiB blocks 19 / 51 us against 211 / 1 187 us of the split encode, 8 GiB 5.0 / 5.0 ms
+// against 7.4 / 7.6 of the ring encoders + k_compact (1 MiB blocks: 5.5 against 20.7; experiments/r06, calls 22, 25)
+#ifndef HSRLE_PPW_MIN_BLOCKS
+#define HSRLE_PPW_MIN_BLOCKS 1u
+#endif
+constexpr uint32_t kPpwMinBlocks = HSRLE_PPW_MIN_BLOCKS;   // (A/B builds: 0xFFFFFFFF = never, also for the monolithic streams)
+static_assert(kEncodeWaveBytes == kPpMaxBlock && kEncodeWaveBytes == kPpwWindow, "the rule's block / window size is the kernels'");
+// the knobs of the encode rule (hsrle_codecs.h: encode_choice), read once; the shipped build has the defaults
+static const EncodeKnobs &encode_knobs()
 {
-  // OFF by default: measured on the 8 GiB headline buffer the overlap does not pay -- 1 130 GiB/s in one piece against 846 / 964 / 1 015 /
-  // 1 063 GiB/s with chunks of 131 072 / 262 144 / 524 288 / 1 048 576 blocks (the compaction's traffic slows the encode kernel by more
-  // than its own 1.8 ms, and every chunk boundary drains the GPU).  HSRLE_ENCODE_CHUNK_BLOCKS=n turns it on for callers that would rather
-  // have the smaller workspace (two chunks of staging slots instead of the whole input's).
-  static const uint32_t v = [] { const uint32_t e = env_u32("HSRLE_ENCODE_CHUNK_BLOCKS", 0); return e ? e : 0xFFFFFFF0u; }();
-  return v;
+#ifdef HSRLE_EXPERIMENTS
+  static const EncodeKnobs k{ knob_u32("HSRLE_PP", 0u), knob_u32("HSRLE_RUNLIST", 0u), knob_u32("HSRLE_ENCODE_WAVE", 0u) != 0u ? kWaveEncodeMaxBlock : 0u, kPpwMinBlocks,
+                              knob_u32("HSRLE_ENCODE_CHUNK_BLOCKS", 0u), SPLIT_ALL };
+#else
+  static const EncodeKnobs k{ 0u, 0u, 0u, kPpwMinBlocks };
+#endif
+  return k;
+}
+// the rule for a codec id: what the row has comes from the launch table
+static EncodeChoice encode_choice_of(int codec, uint64_t U, uint32_t B, SplitRegions have, bool noSplit = false)
+{
+  init_tables();
+  const CodecLaunch &l = g_launch[codec];
+  const EncodeCaps caps{ l.pp != nullptr, l.ppw8 ? PPW_8 : (l.ppwL ? PPW_L : (l.ppwS ? PPW_S : PPW_NONE)), l.menc != nullptr, l.enc != nullptr, l.wenc != nullptr };
+  return encode_choice(kCodecs[codec], caps, U, B, block_count(U, B), have, noSplit, encode_knobs());
 }
 
 // Split encode (hsrle_mono_encode.hip.h): containers with too few blocks for one lane each are encoded chunk by chunk -- the blocks cut behind
 // runs every encoder state stores, like a monolithic stream, with the block starts as forced cuts.  kSplitPieces pieces (= cut finder lanes) per block.
-constexpr uint32_t kSplitEncodeBelow = 131072u;   // blocks: from here on one lane per block fills the device
-constexpr uint32_t kSplitPieces = 4u, kSplitPiecesMax = 8u;             // (the workspace is planned for the larger number: split_pieces())
-
 struct Workspace
 {
   uint64_t nBlocks, chunk, nChunks;
@@ -41,14 +57,12 @@ struct Workspace
   uint64_t offSlots, offSizes, total;
 };
 
-// splitSmall: reserve the split-encode regions for blocks of 1 .. 4 KiB too (the codecs without a run list encoder -- 8 bit Single, 128 bit --
-// take the split encode there: hsrle_codecs.h split_small(); hsrle_compress_workspace_size_codec)
-static Workspace plan_workspace(uint64_t U, uint32_t B, bool splitSmall = false, bool noSplit = false)
+// regions: which split-encode regions to reserve (EncodeChoice::regions; without a codec: what every caller's workspace has)
+static Workspace plan_workspace(uint64_t U, uint32_t B, SplitRegions regions = encode_knobs().generic)
 {
   Workspace w{};                                                          // (regions that are not reserved stay 0)
   w.nBlocks = block_count(U, B);
-  w.chunk = encode_chunk_blocks();
-  if (w.nBlocks < w.chunk + w.chunk / 2u) w.chunk = w.nBlocks;            // no short last chunk: up to 1.5 chunks go in one piece
+  w.chunk = encode_chunk(w.nBlocks, encode_knobs());
   w.nChunks = (w.nBlocks + w.chunk - 1) / w.chunk;
   const uint64_t slotBlocks = w.nChunks > 1 ? 2u * w.chunk : w.nBlocks;
   uint64_t at = 0;
@@ -56,11 +70,10 @@ static Workspace plan_workspace(uint64_t U, uint32_t B, bool splitSmall = false,
   w.offSizes = at; at += align_up(w.nBlocks * 4ull, 256);
   w.levels.lay_out(w.chunk, at);
   // (split encode regions: sized for every codec, but only where the split path can run -- small containers of blocks above 4 KiB; up to
-  //  4 KiB the run list encoders take every codec that has a chunk mode (split_encode_applies), and reserving the regions there cost
-  //  3x the input for nothing: ADVICE r3.  Experiment builds can send those containers to the split path too, HSRLE_RUNLIST=2.)
+  //  4 KiB the run list encoders take every codec that has a chunk mode, and reserving the regions there cost 3x the input for nothing:
+  //  ADVICE r3 -- SPLIT_ALL is for the codecs that have none.  SPLIT_NONE: a codec whose blocks above 4 KiB go to the windowed encoders.)
   w.spPieces = w.nBlocks * kSplitPiecesMax; w.spMaxChunks = w.spPieces + w.nBlocks;
-  // (noSplit: a codec whose blocks above 4 KiB go to the windowed position-parallel encoders never takes the split encode -- its regions, 2.3 x the input, are not reserved)
-  if (!noSplit && w.nBlocks < kSplitEncodeBelow && B >= 1024u && B <= (1u << 20) && (kExperiments || B > 4096u || splitSmall))
+  if (w.nBlocks < kSplitEncodeBelow && B >= 1024u && B <= (1u << 20) && (regions == SPLIT_ALL || (regions == SPLIT_LARGE && B > kEncodeWaveBytes)))
   {
     const uint64_t np = w.spPieces, nc = w.spMaxChunks;
     w.spCutPos = at; at += align_up(8ull * np, 256);
@@ -129,26 +142,6 @@ static uint32_t split_pieces(uint32_t B)
 {
   const uint32_t k = knob_u32("HSRLE_SPLIT_PIECES", kSplitPieces);
   return (k == kSplitPiecesMax && B % (kSplitPiecesMax * 128u) == 0u) ? k : kSplitPieces;
-}
-
-// (round 6: the codecs with a position-parallel encoder -- a pp launcher in their row -- have no run list instantiation any more; callers run behind init_tables())
-// (the codecs with a run list instantiation were: all but Single, 128 bit and Greedy)
-static bool run_list_codec(int codec) { const CodecInfo &ci = kCodecs[codec]; return !is_single(ci) && ci.S != 16 && !ci.greedy && !g_launch[codec].pp; }
-
-static bool split_encode_applies(int codec, uint64_t nBlocks, uint32_t B)
-{
-  // the codecs whose ring encoders have the chunk mode, and (round 4) 8 bit Single and 128 bit with the per-lane chunk encoders of the monolithic path
-  // rle8_multi / rle8_packed_multi / rle8_{3,7}symlut, the plain / Packed / LUT codecs of 2 .. 8 byte symbols and their Short family: the run list encoders take these whole
-  if (run_list_codec(codec) && run_list_applies(nBlocks, B, 1024u, knob_u32("HSRLE_RUNLIST", 0u))) return false;
-  if (nBlocks >= kSplitEncodeBelow || B < 1024u || B > (1u << 20) || (B % (kSplitPieces * 128u)) != 0u) return false;
-  // Greedy: the lists of 3 / 7 symbols decide which runs the scan stores, so a chunk's list is only known when the chunk in front of it is final --
-  // measured (88 MB frame, rle32_7symlut: two full passes + three repair rounds 3.7 ms against 3.1 ms with one lane per block); a list of ONE symbol
-  // behind a stored run is that run's symbol, and the first guess is right
-  const CodecInfo &ci = kCodecs[codec];
-  if (ci.greedy && !greedy_one_symbol_list(ci)) return false;
-  if (is_single(ci) && B > 32768u) return false;   // (the per-block symbol pick holds a block in LDS: hsrle_encode8s.hip.h)
-  init_tables();
-  return g_launch[codec].menc != nullptr;
 }
 
 // Split encode of a container (no host synchronisation: graph capturable like the plain path): cuts inside the blocks -> chunk table (block
@@ -241,40 +234,20 @@ static int compress_split(int codec, const uint8_t *dIn, uint64_t U, uint32_t B,
   return hipGetLastError() == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
 }
 
-// the position-parallel encoder takes the containers of its codecs whose blocks it can hold (HSRLE_PP=1 / 2 in experiment builds: always / never)
-constexpr uint32_t kPpMinBlocks = 1u;       // (faster than the ring and the run list encoders from 1 MiB to 8 GiB: experiments/r05, call 20)
-static bool pp_applies(int codec, uint32_t nBlocks, uint32_t B)
+// The windowed launcher of a codec and the words of its windows' state records: the 8 bit pair 8, the codecs of hsrle_encodeSp.hip.h 16, those of hsrle_encodeLp.hip.h (the
+// list travels with it) 32.  Blocks of a container: ppw8, then ppwL, then ppwS.  Chunks of ONE monolithic stream, for the codecs whose encoder state at a cut is fixed by
+// the cut itself (hsrle_codecs.h: chunk_mode): ppw8, then ppwSM, the chunk mode of hsrle_encodeSpw.hip.h.  Callers run behind init_tables().
+struct PpwPick { PpwLaunch launch; uint32_t stateWords; };
+static PpwPick ppw_pick(int codec, bool chunks)
 {
-  static const uint32_t force = knob_u32("HSRLE_PP", 0u);
-  if (codec < 0 || codec >= kCodecCount || !g_launch[codec].pp || B > kPpMaxBlock || force == 2u) return false;
-  // (the slot area holds the records: pp_scratch_bytes() is less than nBlocks staging slots for every block size)
-  return force == 1u || nBlocks >= kPpMinBlocks;
-}
-
-// ... and, window by window, their containers of blocks above 4 KiB (hsrle_encode8pw.hip.h), whatever their size: 8 MiB of 8 KiB / 64 KiB blocks 19 / 51 us against
-// 211 / 1 187 us of the split encode, 8 GiB 5.0 / 5.0 ms against 7.4 / 7.6 of the ring encoders + k_compact (1 MiB blocks: 5.5 against 20.7; experiments/r06, calls 22, 25)
-#ifndef HSRLE_PPW_MIN_BLOCKS
-#define HSRLE_PPW_MIN_BLOCKS 1u
-#endif
-constexpr uint32_t kPpwMinBlocks = HSRLE_PPW_MIN_BLOCKS;   // (A/B builds: 0xFFFFFFFF = never, also for the monolithic streams)
-// words of a window's state record: the 8 bit pair 8, the codecs of hsrle_encodeSp.hip.h 16, those of hsrle_encodeLp.hip.h (the list travels with it) 32
-static uint32_t ppw_state_words(int codec) { const CodecLaunch &l = g_launch[codec]; return l.ppw8 ? kPpwStateWords : (l.ppwL ? kPpwLStateWords : kPpwSStateWords); }
-static PpwLaunch ppw_launcher(int codec)
-{
-  if (codec < 0 || codec >= kCodecCount) return nullptr;
   const CodecLaunch &l = g_launch[codec];
-  return l.ppw8 ? l.ppw8 : (l.ppwL ? l.ppwL : l.ppwS);
+  if (chunks) return { !chunk_mode(kCodecs[codec]) ? nullptr : (l.ppw8 ? l.ppw8 : l.ppwSM), l.ppw8 ? kPpwStateWords : kPpwSStateWords };
+  return l.ppw8 ? PpwPick{ l.ppw8, kPpwStateWords } : (l.ppwL ? PpwPick{ l.ppwL, kPpwLStateWords } : PpwPick{ l.ppwS, kPpwSStateWords });
 }
-// (the plain / Packed codecs write 8 or 32 bit fields whatever the block size; the LUT / Short forms choose their field widths -- and the reference its penalties, with
-//  thresholds of 0xFFFFF: rleX_Xsl.h:130, rleX_Xsl_short.h:178 -- by the values: below 1 MiB per block no count or range gets there and "every run is stored" holds)
-constexpr uint32_t kPpwListMaxBlock = (1u << 20) - 128u;
-static bool ppw_applies(int codec, uint32_t nBlocks, uint32_t B)
+// states, then (256-byte aligned) the records of nWindows windows from `base` on: the slot area, which the windowed encoders do not stage in
+static void ppw_lay_out(PpwArgs &pa, uint8_t *base, uint32_t stateWords, uint64_t nWindows)
 {
-  static const uint32_t force = knob_u32("HSRLE_PP", 0u);
-  if (!ppw_launcher(codec) || B <= kPpMaxBlock || force == 2u) return false;
-  if (!any_block_windowed(kCodecs[codec]) && B > kPpwListMaxBlock) return false;   // (any block size: 8 bit multi, plain / Packed of 2 .. 8 byte symbols)
-  if ((uint64_t)nBlocks * ((B + kPpwWindow - 1u) / kPpwWindow) > 0xFFFFFFF0ull) return false;            // (windows are counted in 32 bits: 16 TiB)
-  return force == 1u || nBlocks >= kPpwMinBlocks;
+  pa.nWindows = (uint32_t)nWindows; pa.states = (uint32_t *)base; pa.recs = (uint32_t *)(base + align_up(4ull * stateWords * nWindows, 256));
 }
 
 static int compress_async(int codec, const void *dIn, uint64_t U, void *dOut, uint64_t cap, uint32_t B, void *dWs, uint64_t wsSize, hipStream_t st, bool noSplit = false)
@@ -291,19 +264,14 @@ static int compress_async(int codec, const void *dIn, uint64_t U, void *dOut, ui
   if (!device_ok())
     return HSRLE_ERR_DEVICE;
 
-  init_tables();
-  if (!g_launch[codec].enc)
+  // (small containers of 1 .. 4 KiB blocks of the codecs without a run list encoder: the split encode needs regions the general workspace does not reserve -- the
+  //  library's own scratch has them, a caller's workspace if it was sized by hsrle_compress_workspace_size_codec.  The plan reserves them only where the split
+  //  encode will really run: they are 2 - 3 x the input -- ADVICE r4)
+  const SplitRegions have = (dWs == nullptr || wsSize >= plan_workspace(U, B, SPLIT_ALL).total) ? SPLIT_ALL : encode_knobs().generic;
+  const EncodeChoice ec = encode_choice_of(codec, U, B, have, noSplit);
+  if (ec.path == ENC_UNSUPPORTED)
     return HSRLE_ERR_UNSUPPORTED;
-
-  // (8 bit Single / 128 bit, small containers of 1 .. 4 KiB blocks: the split encode needs regions the general workspace does not reserve --
-  //  the library's own scratch has them, a caller's workspace if it was sized by hsrle_compress_workspace_size_codec)
-  Workspace w = plan_workspace(U, B, false, ppw_applies(codec, (uint32_t)block_count(U, B), B));
-  if (!noSplit && split_small(kCodecs[codec]) && B <= 4096u && !pp_applies(codec, (uint32_t)w.nBlocks, B))
-  {
-    // (only where the split encode will really run: its regions are 2 - 3 x the input -- ADVICE r4)
-    const Workspace w2 = plan_workspace(U, B, true);
-    if (w2.spSlots != 0 && split_encode_applies(codec, w2.nBlocks, B) && (dWs == nullptr || wsSize >= w2.total)) w = w2;
-  }
+  const Workspace w = plan_workspace(U, B, ec.regions);
 
   void *own = nullptr;
   if (dWs == nullptr)
@@ -326,16 +294,24 @@ static int compress_async(int codec, const void *dIn, uint64_t U, void *dOut, ui
   int rc = HSRLE_OK;
   bool finished = false;                                                // (small containers: the size scan's launch wrote header and tail pad)
 
-  // HSRLE_ENCODE_WAVE=1: rle8_multi / rle8_packed_multi with blocks of at most 4 KiB by ONE WAVE PER BLOCK (hsrle_encode8w.hip.h: position
-  // parallel run detection, offsets by decoupled look-back, the payload written once, no staging slots and no compaction pass).  Bit-exact
-  // (every block of the 8 GiB buffer against the reference manifest), but OFF by default: at 4 KiB per wave the kernel is bound by the
-  // latency chain of one block, not by traffic -- 8 GiB: 13.5 ms against 7.4 ms of the lane-per-block kernel + compaction (input load + masks
-  // 2.1 ms, run list 0.7, decisions 2.1, packets 2.6, look-back 1.4 .. 5.9 ms).
-  hipStream_t aux = w.nChunks > 1 ? aux_stream() : nullptr;
-#ifdef HSRLE_EXPERIMENTS
-  static const bool waveEncode = env_u32("HSRLE_ENCODE_WAVE", 0) != 0u;
-  if (waveEncode && g_launch[codec].wenc && B <= kWaveEncodeMaxBlock)
+  // sizes -> offsets.  Small containers: in ONE launch that writes header and tail pad too -- it reads the sizes 16 bytes at a time, and a caller's workspace may sit anywhere
+  auto scan_and_place = [&]() -> bool {
+    if (nBlocks > kScanSmallMax || (((uintptr_t)sizes) & 15u) != 0u)
+      return scan_sizes(sizes, nBlocks, offsets, ws, w.levels, st) == hipSuccess;
+    hipLaunchKernelGGL(k_scan_small_finish, dim3((nBlocks + kScanTile - 1u) / kScanTile), dim3(kScanThreads), 0, st, (const uint32_t *)sizes, nBlocks, offsets, container, (uint32_t)codec, U, B);
+    finished = true;
+    return true;
+  };
+  switch (ec.path)
   {
+#ifdef HSRLE_EXPERIMENTS
+  case ENC_WAVE:
+  {
+    // HSRLE_ENCODE_WAVE=1: rle8_multi / rle8_packed_multi with blocks of at most 4 KiB by ONE WAVE PER BLOCK (hsrle_encode8w.hip.h: position
+    // parallel run detection, offsets by decoupled look-back, the payload written once, no staging slots and no compaction pass).  Bit-exact
+    // (every block of the 8 GiB buffer against the reference manifest), but OFF by default: at 4 KiB per wave the kernel is bound by the
+    // latency chain of one block, not by traffic -- 8 GiB: 13.5 ms against 7.4 ms of the lane-per-block kernel + compaction (input load + masks
+    // 2.1 ms, run list 0.7, decisions 2.1, packets 2.6, look-back 1.4 .. 5.9 ms).
     // (the slot area of the lane-per-block path is not needed: the tile words and the ticket counters live at its start)
     uint32_t *ticket = (uint32_t *)(ws + w.offSlots);
     unsigned long long *tiles = (unsigned long long *)(ws + w.offSlots + kTicketBytes);
@@ -343,77 +319,51 @@ static int compress_async(int codec, const void *dIn, uint64_t U, void *dOut, ui
     if (w.offSizes - w.offSlots < kTicketBytes + 8ull * nBlocks) rc = HSRLE_ERR_CAPACITY;
     else if (zero_async(ticket, kTicketBytes + 8ull * nBlocks, st) != hipSuccess || g_launch[codec].wenc(wa, st) != hipSuccess)
       rc = HSRLE_ERR_DEVICE;
+    break;
   }
-  else
 #endif
-  if (w.nChunks <= 1 && pp_applies(codec, nBlocks, B))
+  case ENC_PP:
   {
     // position-parallel encoder (hsrle_encode8p.hip.h): sizes + one record per stored run, scan, then every stream written once to its final place --
-    // no staging slots, no compaction.  The records live in the (otherwise unused) slot area.
+    // no staging slots, no compaction.  The records live in the (otherwise unused) slot area: pp_scratch_bytes() is less than nBlocks staging slots for every block size.
     PpArgs pa{ (const uint8_t *)dIn, U, B, nBlocks, sizes, offsets, payload, ws + w.offSlots };
-    if (g_launch[codec].pp(pa, 0, st) != hipSuccess)
+    if (g_launch[codec].pp(pa, 0, st) != hipSuccess || !scan_and_place() || g_launch[codec].pp(pa, 1, st) != hipSuccess)
       rc = HSRLE_ERR_DEVICE;
-    else if (nBlocks <= kScanSmallMax && (((uintptr_t)sizes) & 15u) == 0u)   // (the one-launch scan reads the sizes 16 bytes at a time: a caller's workspace may sit anywhere)
-    {
-      hipLaunchKernelGGL(k_scan_small_finish, dim3((nBlocks + kScanTile - 1u) / kScanTile), dim3(kScanThreads), 0, st, (const uint32_t *)sizes, nBlocks, offsets, container, (uint32_t)codec, U, B);
-      finished = true;
-    }
-    else if (scan_sizes(sizes, nBlocks, offsets, ws, w.levels, st) != hipSuccess)
-      rc = HSRLE_ERR_DEVICE;
-    if (rc == HSRLE_OK && g_launch[codec].pp(pa, 1, st) != hipSuccess)
-      rc = HSRLE_ERR_DEVICE;
+    break;
   }
-  else if (w.nChunks <= 1 && ppw_applies(codec, nBlocks, B))
+  case ENC_PPW:
   {
     // the same encoder, a block walked in windows of 4 KiB: a wave per block leaves sizes, window states and records; after the scan a wave per window writes
     // the packets of the runs that end in it.  States and records live in the slot area (1 056 bytes per window).
+    const PpwPick pick = ppw_pick(codec, false);
     PpwArgs pa{};
     pa.in = (const uint8_t *)dIn; pa.U = U; pa.B = B; pa.nUnits = nBlocks; pa.sizes = sizes; pa.offsets = offsets; pa.payload = payload;
-    pa.nWindows = nBlocks * ((B + kPpwWindow - 1u) / kPpwWindow);
-    pa.states = (uint32_t *)(ws + w.offSlots);
-    pa.recs = (uint32_t *)(ws + w.offSlots + align_up(4ull * ppw_state_words(codec) * pa.nWindows, 256));
-    const PpwLaunch launch = ppw_launcher(codec);
-    if (launch(pa, 0, st) != hipSuccess)
+    ppw_lay_out(pa, ws + w.offSlots, pick.stateWords, (uint64_t)nBlocks * ((B + kPpwWindow - 1u) / kPpwWindow));
+    if (pick.launch(pa, 0, st) != hipSuccess || !scan_and_place() || pick.launch(pa, 1, st) != hipSuccess)
       rc = HSRLE_ERR_DEVICE;
-    else if (nBlocks <= kScanSmallMax && (((uintptr_t)sizes) & 15u) == 0u)
-    {
-      hipLaunchKernelGGL(k_scan_small_finish, dim3((nBlocks + kScanTile - 1u) / kScanTile), dim3(kScanThreads), 0, st, (const uint32_t *)sizes, nBlocks, offsets, container, (uint32_t)codec, U, B);
-      finished = true;
-    }
-    else if (scan_sizes(sizes, nBlocks, offsets, ws, w.levels, st) != hipSuccess)
-      rc = HSRLE_ERR_DEVICE;
-    if (rc == HSRLE_OK && launch(pa, 1, st) != hipSuccess)
-      rc = HSRLE_ERR_DEVICE;
+    break;
   }
-  else if (w.nChunks <= 1 && w.spSlots != 0 && split_encode_applies(codec, w.nBlocks, B))
-  {
+  case ENC_SPLIT:
     rc = compress_split(codec, (const uint8_t *)dIn, U, B, nBlocks, ws, w, offsets, payload, st);
     finished = true;                                                    // (k_split_finish wrote header and tail pad)
-  }
-  else if (w.nChunks > 1 && aux == nullptr)
-    rc = HSRLE_ERR_DEVICE;
-  else if (w.nChunks <= 1)
+    break;
+  case ENC_RING:
   {
     EncodeArgs ea{ (const uint8_t *)dIn, U, B, nBlocks, ws + w.offSlots, stride, sizes };
     ea.ringSel = (uint32_t *)(ws + w.offSlots + align_up((uint64_t)nBlocks * stride, 256));   // (in the wave encoder's counter area behind the slots: unused on this path)
-    if (g_launch[codec].enc(ea, st) != hipSuccess)
+    if (g_launch[codec].enc(ea, st) != hipSuccess || !scan_and_place())
       rc = HSRLE_ERR_DEVICE;
-    else if (nBlocks <= kScanSmallMax && (((uintptr_t)sizes) & 15u) == 0u)   // (the one-launch scan reads the sizes 16 bytes at a time: a caller's workspace may sit anywhere)
-    {
-      hipLaunchKernelGGL(k_scan_small_finish, dim3((nBlocks + kScanTile - 1u) / kScanTile), dim3(kScanThreads), 0, st, (const uint32_t *)sizes, nBlocks, offsets, container, (uint32_t)codec, U, B);
-      finished = true;
-    }
-    else if (scan_sizes(sizes, nBlocks, offsets, ws, w.levels, st) != hipSuccess)
-      rc = HSRLE_ERR_DEVICE;
-    if (rc == HSRLE_OK)
+    else
       hipLaunchKernelGGL(k_compact, dim3((nBlocks + 3u) / 4u), dim3(256), 0, st, ea.slots, stride, (const uint64_t *)offsets, payload, nBlocks);
+    break;
   }
-  else
+  default:   // ENC_RING_CHUNKS
   {
     // chunk k: encode + size scan on the caller's stream, compaction on the second stream; the slot buffer of chunk k is free again when
     // the compaction of chunk k - 2 is done
+    const hipStream_t aux = aux_stream();
     hipEvent_t scanned = nullptr, compacted[2] = { nullptr, nullptr };
-    bool ok = hipEventCreateWithFlags(&scanned, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&compacted[0], hipEventDisableTiming) == hipSuccess &&
+    bool ok = aux != nullptr && hipEventCreateWithFlags(&scanned, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&compacted[0], hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&compacted[1], hipEventDisableTiming) == hipSuccess;
     for (uint64_t k = 0; k < w.nChunks && ok; k++)
     {
@@ -434,6 +384,7 @@ static int compress_async(int codec, const void *dIn, uint64_t U, void *dOut, ui
     if (compacted[0]) (void)hipEventDestroy(compacted[0]);
     if (compacted[1]) (void)hipEventDestroy(compacted[1]);
     if (!ok) rc = HSRLE_ERR_DEVICE;
+  }
   }
   if (rc == HSRLE_OK && !finished)
   {
@@ -466,30 +417,33 @@ static int check_info(const ContainerHeader &h, uint64_t containerSize, hsrle_co
   return HSRLE_OK;
 }
 
+// THE prologue of the decode entry points: the argument checks in their observable order (hsrle_codecs.h: a null pointer beats a bad info, which beats a bad range, which
+// beats the capacity), then the device, then the launch arguments.  HSRLE_OK with count == 0: nothing to launch -- the entry returns it, behind the device check.
+static int decode_prologue(const void *dContainer, const hsrle_container_info_t *info, uint32_t first, uint32_t count, void *dOut, uint64_t cap, uint32_t *dStatus, DecodeArgs *da)
+{
+  int rc = decode_info_check(dContainer, info, dOut);
+  if (rc == HSRLE_OK) rc = decode_range_check(*info, first, count, cap);
+  if (rc != HSRLE_OK)
+    return rc;
+  if (!device_ok())
+    return HSRLE_ERR_DEVICE;
+  init_tables();
+  const uint8_t *container = (const uint8_t *)dContainer;
+  const uint8_t *payload = container + HSRLE_CONTAINER_HEADER_SIZE + 8ull * ((uint64_t)info->blockCount + 1ull);
+  *da = DecodeArgs{ payload, (const uint64_t *)(container + HSRLE_CONTAINER_HEADER_SIZE), payload + info->payloadSize + HSRLE_CONTAINER_TAIL_PAD,
+                    (uint8_t *)dOut, info->uncompressedSize, info->blockSize, first, count, dStatus };
+  return HSRLE_OK;
+}
+
 static int decompress_blocks_async(const void *dContainer, const hsrle_container_info_t *info, uint32_t first, uint32_t count, void *dOut, uint64_t cap,
                                    uint32_t *dStatus, hipStream_t st)
 {
-  if (dContainer == nullptr || info == nullptr || dOut == nullptr)
-    return HSRLE_ERR_ARGUMENT;
-  if (info->codec >= (uint32_t)kCodecCount || !valid_block_size(info->blockSize) || info->blockCount != block_count(info->uncompressedSize, info->blockSize))
-    return HSRLE_ERR_FORMAT;
-  if ((uint64_t)first + count > info->blockCount)
-    return HSRLE_ERR_ARGUMENT;
-  if (cap < info->uncompressedSize)
-    return HSRLE_ERR_CAPACITY;
-  if (!device_ok())
-    return HSRLE_ERR_DEVICE;
-  if (count == 0)
-    return HSRLE_OK;
-
-  init_tables();
+  DecodeArgs da;
+  const int rc = decode_prologue(dContainer, info, first, count, dOut, cap, dStatus, &da);
+  if (rc != HSRLE_OK || count == 0)
+    return rc;
   if (!g_launch[info->codec].dec)
     return HSRLE_ERR_UNSUPPORTED;
-
-  const uint8_t *container = (const uint8_t *)dContainer;
-  const uint8_t *payload = container + HSRLE_CONTAINER_HEADER_SIZE + 8ull * ((uint64_t)info->blockCount + 1ull);
-  DecodeArgs da{ payload, (const uint64_t *)(container + HSRLE_CONTAINER_HEADER_SIZE), payload + info->payloadSize + HSRLE_CONTAINER_TAIL_PAD,
-                 (uint8_t *)dOut, info->uncompressedSize, info->blockSize, first, count, dStatus };
   return g_launch[info->codec].dec(da, st) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
 }
 
@@ -526,22 +480,17 @@ static uint32_t split_sub_block(const hsrle_container_info_t *info, uint32_t wan
 static int decompress_split_async(const void *dContainer, const hsrle_container_info_t *info, uint32_t first, uint32_t count, void *dOut, uint64_t cap, uint32_t *dStatus,
                                   void *dWs, uint64_t wsSize, uint32_t subBlock, hipStream_t st)
 {
-  if (dContainer == nullptr || info == nullptr || dOut == nullptr)
-    return HSRLE_ERR_ARGUMENT;
-  if (info->codec >= (uint32_t)kCodecCount || !valid_block_size(info->blockSize) || info->blockCount != block_count(info->uncompressedSize, info->blockSize))
-    return HSRLE_ERR_FORMAT;
+  // (no split -> the plain decode: decided on a good info, before the range and the capacity are looked at)
+  int rc = decode_info_check(dContainer, info, dOut);
+  if (rc != HSRLE_OK)
+    return rc;
   const uint32_t SB = split_sub_block(info, subBlock);
   if (SB == info->blockSize)
     return decompress_blocks_async(dContainer, info, first, count, dOut, cap, dStatus, st);
-  if ((uint64_t)first + count > info->blockCount)
-    return HSRLE_ERR_ARGUMENT;
-  if (cap < info->uncompressedSize)
-    return HSRLE_ERR_CAPACITY;
-  if (!device_ok())
-    return HSRLE_ERR_DEVICE;
-  if (count == 0)
-    return HSRLE_OK;
-  init_tables();
+  DecodeArgs da;
+  rc = decode_prologue(dContainer, info, first, count, dOut, cap, dStatus, &da);
+  if (rc != HSRLE_OK || count == 0)
+    return rc;
   if (!g_launch[info->codec].dec || !g_launch[info->codec].sub)
     return HSRLE_ERR_UNSUPPORTED;
 
@@ -550,10 +499,6 @@ static int decompress_split_async(const void *dContainer, const hsrle_container_
     const uint64_t countsBytes = packet_list_counts_bytes(count);
     if (dWs == nullptr || ((uintptr_t)dWs & 15u) != 0u || wsSize < countsBytes + (uint64_t)count * packet_list_cap(info->blockSize) * 8ull)
       return HSRLE_ERR_CAPACITY;
-    const uint8_t *container = (const uint8_t *)dContainer;
-    const uint8_t *payload = container + HSRLE_CONTAINER_HEADER_SIZE + 8ull * ((uint64_t)info->blockCount + 1ull);
-    DecodeArgs da{ payload, (const uint64_t *)(container + HSRLE_CONTAINER_HEADER_SIZE), payload + info->payloadSize + HSRLE_CONTAINER_TAIL_PAD,
-                   (uint8_t *)dOut, info->uncompressedSize, info->blockSize, first, count, dStatus };
     if (g_launch[info->codec].sub(da, kSubPacketList, (uint32_t *)dWs, st) != hipSuccess)
       return HSRLE_ERR_DEVICE;
     return launch_expand_packets(kCodecs[info->codec].S, da, (const uint64_t *)((const uint8_t *)dWs + countsBytes), (const uint32_t *)dWs, st) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
@@ -569,10 +514,6 @@ static int decompress_split_async(const void *dContainer, const hsrle_container_
   if (dWs == nullptr || wsSize < (subEnd - subFirst) * 4ull * kEntryRecDwords)
     return HSRLE_ERR_CAPACITY;
 
-  const uint8_t *container = (const uint8_t *)dContainer;
-  const uint8_t *payload = container + HSRLE_CONTAINER_HEADER_SIZE + 8ull * ((uint64_t)info->blockCount + 1ull);
-  DecodeArgs da{ payload, (const uint64_t *)(container + HSRLE_CONTAINER_HEADER_SIZE), payload + info->payloadSize + HSRLE_CONTAINER_TAIL_PAD,
-                 (uint8_t *)dOut, info->uncompressedSize, info->blockSize, first, count, dStatus };
   // records are indexed by the global sub-block number: hand the kernel the address record 0 would have
   uint32_t *rec0 = (uint32_t *)((uintptr_t)dWs - (uintptr_t)(subFirst * 4ull * kEntryRecDwords));
   if (g_launch[info->codec].sub(da, SB, rec0, st) != hipSuccess)
@@ -586,27 +527,17 @@ static int decompress_split_async(const void *dContainer, const hsrle_container_
 constexpr uint32_t kWaveDecodeBelow = 65536u;     // blocks: above, one lane per block has the waves it needs
 static int decompress_wave_async(const void *dContainer, const hsrle_container_info_t *info, uint32_t first, uint32_t count, void *dOut, uint64_t cap, uint32_t *dStatus, hipStream_t st)
 {
-  if (dContainer == nullptr || info == nullptr || dOut == nullptr)
-    return HSRLE_ERR_ARGUMENT;
-  if (info->codec >= (uint32_t)kCodecCount || !valid_block_size(info->blockSize) || info->blockCount != block_count(info->uncompressedSize, info->blockSize))
-    return HSRLE_ERR_FORMAT;
+  int rc = decode_info_check(dContainer, info, dOut);
+  if (rc != HSRLE_OK)
+    return rc;
   if (info->blockSize > 16384u || !kExperiments)                        // (the wave-per-block decoder is not part of the shipped build: measured slower than the split decode)
     return HSRLE_ERR_UNSUPPORTED;
-  if ((uint64_t)first + count > info->blockCount)
-    return HSRLE_ERR_ARGUMENT;
-  if (cap < info->uncompressedSize)
-    return HSRLE_ERR_CAPACITY;
-  if (!device_ok())
-    return HSRLE_ERR_DEVICE;
-  if (count == 0)
-    return HSRLE_OK;
-  init_tables();
+  DecodeArgs da;
+  rc = decode_prologue(dContainer, info, first, count, dOut, cap, dStatus, &da);
+  if (rc != HSRLE_OK || count == 0)
+    return rc;
   if (!g_launch[info->codec].sub)
     return HSRLE_ERR_UNSUPPORTED;
-  const uint8_t *container = (const uint8_t *)dContainer;
-  const uint8_t *payload = container + HSRLE_CONTAINER_HEADER_SIZE + 8ull * ((uint64_t)info->blockCount + 1ull);
-  DecodeArgs da{ payload, (const uint64_t *)(container + HSRLE_CONTAINER_HEADER_SIZE), payload + info->payloadSize + HSRLE_CONTAINER_TAIL_PAD,
-                 (uint8_t *)dOut, info->uncompressedSize, info->blockSize, first, count, dStatus };
   return g_launch[info->codec].sub(da, 0u, nullptr, st) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;     // (sub-block size 0 = the wave decoder)
 }
 

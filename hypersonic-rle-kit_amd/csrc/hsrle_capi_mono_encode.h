@@ -21,10 +21,8 @@ struct MonoEncPlan
   uint64_t offJobs; uint32_t jobCap;                   // 8 bit Single: literal stretches noted by the chunk encoders for k_copy_jobs
 };
 
-// the codecs whose encoder state at a cut is fixed by the cut itself (hsrle_codecs.h: chunk_mode): the 8 bit pair's windowed encoder, or the chunk mode of hsrle_encodeSpw.hip.h
-static PpwLaunch mono_ppw_launcher(int codec) { return !chunk_mode(kCodecs[codec]) ? nullptr : (g_launch[codec].ppw8 ? g_launch[codec].ppw8 : g_launch[codec].ppwSM); }
-static uint32_t mono_ppw_state_words(int codec) { return g_launch[codec].ppw8 ? kPpwStateWords : kPpwSStateWords; }
-static bool mono_windowed(int codec) { return mono_ppw_launcher(codec) != nullptr && kPpwMinBlocks != 0xFFFFFFFFu && knob_u32("HSRLE_PP", 0u) != 2u; }
+// the codecs whose chunks have a windowed launcher (hsrle_capi_container.h: ppw_pick), unless an A/B build or HSRLE_PP=2 (read per call: tools/mono_encode_time.py) says never
+static bool mono_windowed(int codec) { return ppw_pick(codec, true).launch != nullptr && kPpwMinBlocks != 0xFFFFFFFFu && knob_u32("HSRLE_PP", 0u) != 2u; }
 
 static MonoEncPlan plan_mono_encode(uint32_t U, int codec, bool lists = true)
 {
@@ -67,7 +65,7 @@ static MonoEncPlan plan_mono_encode(uint32_t U, int codec, bool lists = true)
   // (windowed: no staging slots -- the window states and records live there: 32 (8 bit) / 64 + 1 024 bytes per window, at most U / 4 096 + chunks windows)
   const uint64_t windowsMax = ((uint64_t)U >> 12) + n + 1ull;
   const uint64_t slotBytes = (uint64_t)U + ((uint64_t)U >> 7) + 256ull * (n + 2) + 4096ull;
-  const uint64_t windowBytes = align_up(4ull * mono_ppw_state_words(codec) * windowsMax, 256) + 4ull * kPpwStride * windowsMax + 512ull;
+  const uint64_t windowBytes = align_up(4ull * ppw_pick(codec, true).stateWords * windowsMax, 256) + 4ull * kPpwStride * windowsMax + 512ull;
   m.offSlots = at; at += align_up(m.windowed && windowBytes > slotBytes ? windowBytes : slotBytes, 256);
   m.total = at;
   return m;
@@ -130,15 +128,13 @@ static int mono_encode_dev(int codec, const uint8_t *dIn, uint32_t U, uint8_t *d
   {
     // every piece may be a chunk: a wave per possible chunk (those behind the last one write a zero size), a wave per possible window -- nothing is read back
     // before the end
-    const PpwLaunch launch = mono_ppw_launcher(codec);
+    const PpwPick pick = ppw_pick(codec, true);
     PpwArgs pa{};
     pa.in = dIn; pa.U = U; pa.B = 0u; pa.nUnits = m.pieces + 1u; pa.starts = starts; pa.syms = syms; pa.count = ctrl; pa.sizes = sizes; pa.offsets = offsets; pa.payload = dOut + hs;
-    pa.nWindows = (uint32_t)windowsMax;
-    pa.states = (uint32_t *)(ws + m.offSlots);
-    pa.recs = (uint32_t *)(ws + m.offSlots + align_up(4ull * mono_ppw_state_words(codec) * windowsMax, 256));
+    ppw_lay_out(pa, ws + m.offSlots, pick.stateWords, windowsMax);
     pa.fail = ctrl + 5;                                                   // (zeroed above)
     g_monoEncLast[0] = g_monoEncLast[1] = g_monoEncLast[2] = g_monoEncLast[3] = 0u;   // (no list, no rounds)
-    if (launch(pa, 0, st) != hipSuccess || scan_sizes(sizes, pa.nUnits, offsets, ws, w, st) != hipSuccess || launch(pa, 1, st) != hipSuccess)
+    if (pick.launch(pa, 0, st) != hipSuccess || scan_sizes(sizes, pa.nUnits, offsets, ws, w, st) != hipSuccess || pick.launch(pa, 1, st) != hipSuccess)
       return HSRLE_ERR_DEVICE;
     hipLaunchKernelGGL(k_mono_finish, dim3(1), dim3(64), 0, st, dOut, U, hs, (const uint64_t *)offsets, (const uint32_t *)ctrl, ctrl, 0u);
     if (pSize == nullptr)

@@ -121,9 +121,9 @@ constexpr uint32_t cut_long(const CodecInfo &c)
 // the codecs whose encoder state at a cut is fixed by the cut itself (no list, or a one-symbol list = the cut's symbol): plain / Packed / Short without or with a
 // one-symbol list, of 1 .. 8 byte symbols -- the chunks of their monolithic streams go to the windowed position-parallel encoders
 constexpr bool chunk_mode(const CodecInfo &c) { return (c.fam == PLAIN || c.fam == PACKED || c.fam == SHORT0 || c.fam == SHORT1) && c.S <= 8 && !c.greedy; }
-// windowed encoders, blocks of ANY size: plain / Packed of 1 .. 8 byte symbols write 8 or 32 bit fields whatever the block size (hsrle_capi_container.h: ppw_applies)
+// windowed encoders, blocks of ANY size: plain / Packed of 1 .. 8 byte symbols write 8 or 32 bit fields whatever the block size (encode_choice)
 constexpr bool any_block_windowed(const CodecInfo &c) { return (c.fam == PLAIN || c.fam == PACKED) && c.S <= 8; }
-// Greedy with a list of ONE symbol: behind a stored run the list is that run's symbol, so a chunk's first guess is right (split_encode_applies)
+// Greedy with a list of ONE symbol: behind a stored run the list is that run's symbol, so a chunk's first guess is right (encode_choice: the split encode)
 constexpr bool greedy_one_symbol_list(const CodecInfo &c) { return c.greedy && c.fam == SHORT1; }
 // the codecs that have a many-lane chunk encoder but no run list encoder: small containers of 1 .. 4 KiB blocks take the split encode IF the
 // caller's workspace has its regions (hsrle_compress_workspace_size_codec; the library's own scratch always has)
@@ -180,6 +180,91 @@ constexpr DecodeVariant decode_variant(const CodecInfo &c, bool window, bool ent
   // rle32_3symlut_byte +6 %, rle48_7symlut_sym +4 %, rle64_sym +-0; the 128 bit codecs +10 %)
   if (entries || (k.alwaysEnt && c.S >= 3 && c.S <= 8)) return { fam, true, true, false, 128, false, false };
   return { fam, true, false, false, small ? 64 : 128, false, false };
+}
+
+// ---- container encode: which encoder takes a container, and which workspace regions it needs.  THE rule (DESIGN.md 4.2 has it as a table); compress_async,
+// hsrle_encode_path and hsrle_compress_workspace_size_codec all ask it (hsrle_capi_container.h: encode_choice_of) ----
+constexpr uint32_t kEncodeWaveBytes = 4096u;        // what a wave of the position-parallel encoders holds (= kPpMaxBlock = kPpwWindow: hsrle_capi_container.h asserts it)
+constexpr uint32_t kSplitEncodeBelow = 131072u;     // blocks: from here on one lane per block fills the device -- no split encode, no run list
+constexpr uint32_t kSplitPieces = 4u, kSplitPiecesMax = 8u;   // cut finder lanes per block of the split encode (the workspace is planned for the larger number: split_pieces())
+// (the plain / Packed codecs write 8 or 32 bit fields whatever the block size; the LUT / Short forms choose their field widths -- and the reference its penalties, with
+//  thresholds of 0xFFFFF: rleX_Xsl.h:130, rleX_Xsl_short.h:178 -- by the values: below 1 MiB per block no count or range gets there and "every run is stored" holds)
+constexpr uint32_t kPpwListMaxBlock = (1u << 20) - 128u;
+
+enum PpwKind : int { PPW_NONE = 0, PPW_8, PPW_L, PPW_S };   // which windowed launcher a row has (CodecLaunch::ppw8, then ppwL, then ppwS)
+// what a row of the launch table has; the host fills it from g_launch[codec] (wenc: experiment builds, the wave encoder of rle8_multi / rle8_packed_multi)
+struct EncodeCaps { bool pp; PpwKind ppw; bool menc, enc; bool wenc = false; };
+// the split encode's regions in a workspace (2 - 3 x the input): none, those of blocks above 4 KiB (every workspace sized without a codec has them), or those of the
+// split_small() codecs' blocks of 1 .. 4 KiB too (the library's own scratch, a workspace of hsrle_compress_workspace_size_codec)
+enum SplitRegions : int { SPLIT_NONE = 0, SPLIT_LARGE = 1, SPLIT_ALL = 2 };
+struct EncodeKnobs   // experiment builds (hsrle_capi_container.h: encode_knobs); the shipped library passes the defaults
+{
+  uint32_t pp = 0u;             // HSRLE_PP: 1 = the position-parallel encoders always, 2 = never
+  uint32_t runList = 0u;        // HSRLE_RUNLIST: 1 = the run list encoders always, 2 = never
+  uint32_t waveMaxBlock = 0u;   // HSRLE_ENCODE_WAVE=1: blocks up to this size go to the wave encoder (0: off)
+  uint32_t ppwMinBlocks = 1u;   // -DHSRLE_PPW_MIN_BLOCKS (0xFFFFFFFF = never windowed)
+  uint32_t chunkBlocks = 0u;    // HSRLE_ENCODE_CHUNK_BLOCKS: the ring encoders take the container in chunks of so many blocks (0: in one piece)
+  SplitRegions generic = SPLIT_LARGE;   // what a workspace sized without a codec reserves (experiment builds: SPLIT_ALL, so that HSRLE_RUNLIST=2 can send small blocks to the split encode)
+};
+enum EncodePath : int { ENC_UNSUPPORTED = 0, ENC_WAVE, ENC_PP, ENC_PPW, ENC_SPLIT, ENC_RING_CHUNKS, ENC_RING };
+// ppw: the windowed launcher of ENC_PPW; runList: ENC_RING's launcher hands the container to the run list encoder (hsrle_encode8r.hip.h); regions: what the path's workspace is planned with
+struct EncodeChoice { EncodePath path; PpwKind ppw; bool runList; SplitRegions regions; };
+// blocks per chunk of the ring encoders (EncodeKnobs::chunkBlocks; else the whole container).  No short last chunk: up to 1.5 chunks go in one piece
+constexpr uint64_t encode_chunk(uint64_t nBlocks, EncodeKnobs k)
+{
+  const uint64_t chunk = k.chunkBlocks ? k.chunkBlocks : 0xFFFFFFF0ull;
+  return nBlocks < chunk + chunk / 2u ? nBlocks : chunk;
+}
+
+// which containers the run list encoder takes (hsrle_encode8r.hip.h; the ring launchers of inst_w8.hip ask too; force: 1 always, 2 never -- experiment builds)
+constexpr bool run_list_applies(uint64_t nBlocks, uint32_t B, uint64_t U, uint32_t force = 0u)
+{
+  return B >= 1024u && B <= kEncodeWaveBytes && U >= 1024u && force != 2u && (force == 1u || nBlocks < kSplitEncodeBelow);
+}
+// (round 6: the codecs with a position-parallel encoder have no run list instantiation any more; before, all but Single, 128 bit and Greedy had one)
+constexpr bool run_list_codec(const CodecInfo &c, EncodeCaps caps) { return !is_single(c) && c.S != 16 && !c.greedy && !caps.pp; }
+
+// have: the split regions of the workspace at hand.  noSplit: the second attempt of hsrle_compress_dev, after the split encode struck its own container.
+constexpr EncodeChoice encode_choice(const CodecInfo &c, EncodeCaps caps, uint64_t U, uint32_t B, uint64_t nBlocks, SplitRegions have, bool noSplit, EncodeKnobs k = EncodeKnobs{})
+{
+  const bool onePiece = nBlocks <= encode_chunk(nBlocks, k);
+  const bool small = B <= kEncodeWaveBytes;
+  // position-parallel: a block per wave, whatever the container's size (faster than the ring and the run list encoders from 1 MiB to 8 GiB: experiments/r05, call 20); above
+  // 4 KiB window by window -- the list codecs below 1 MiB per block only, and the windows are counted in 32 bits (16 TiB)
+  const bool ppOn = k.pp != 2u, pp = caps.pp && small && ppOn;
+  const bool ppw = caps.ppw != PPW_NONE && !small && ppOn && (any_block_windowed(c) || B <= kPpwListMaxBlock) && nBlocks * ((B + kEncodeWaveBytes - 1u) / kEncodeWaveBytes) <= 0xFFFFFFF0ull &&
+                   (k.pp == 1u || nBlocks >= k.ppwMinBlocks);
+  // noSplit suppresses only the upgrade to the small-block regions: a workspace planned without a codec keeps its split path (ADVICE r6 item 1 -- to fix it, let noSplit give SPLIT_NONE here)
+  const SplitRegions has = (noSplit && have == SPLIT_ALL) ? k.generic : have;
+  // (a windowed codec's workspace is planned without the regions; up to 4 KiB they serve the codecs that have no run list encoder)
+  const bool regionsHere = !ppw && (small ? has == SPLIT_ALL && (split_small(c) || k.generic == SPLIT_ALL) : has != SPLIT_NONE);
+  const bool runList = run_list_codec(c, caps) && run_list_applies(nBlocks, B, U, k.runList);
+  // split encode: the codecs with a chunk encoder (the ring encoders' chunk mode; 8 bit Single and 128 bit: the per-lane chunk encoders of the monolithic path), unless the run
+  // list encoders take the container whole.  Greedy: the lists of 3 / 7 symbols decide which runs the scan stores, so a chunk's list is only known when the chunk in front of it
+  // is final -- measured (88 MB frame, rle32_7symlut: two full passes + three repair rounds 3.7 ms against 3.1 ms with one lane per block); a list of ONE symbol behind a stored
+  // run is that run's symbol, and the first guess is right.  Single: the per-block symbol pick holds a block in LDS (hsrle_encode8s.hip.h).
+  const bool split = regionsHere && caps.menc && !(run_list_codec(c, caps) && run_list_applies(nBlocks, B, 1024u, k.runList)) && nBlocks < kSplitEncodeBelow && B >= 1024u && B <= (1u << 20) &&
+                     B % (kSplitPieces * 128u) == 0u && !(c.greedy && !greedy_one_symbol_list(c)) && !(is_single(c) && B > 32768u);
+  const EncodePath path = !caps.enc ? ENC_UNSUPPORTED : (caps.wenc && B <= k.waveMaxBlock) ? ENC_WAVE                                 // (in chunks: the ring encoders only)
+                        : (onePiece && pp) ? ENC_PP : (onePiece && ppw) ? ENC_PPW : (onePiece && split) ? ENC_SPLIT : !onePiece ? ENC_RING_CHUNKS : ENC_RING;
+  const SplitRegions regions = ppw ? SPLIT_NONE : ((path == ENC_SPLIT && small) ? SPLIT_ALL : k.generic);
+  return { path, path == ENC_PPW ? caps.ppw : PPW_NONE, path == ENC_RING && runList, regions };
+}
+
+// ---- container decode: the argument checks of every decode entry point (hsrle_capi_container.h: decode_prologue), in their observable order; no device is asked ----
+constexpr bool valid_block_size(uint32_t B) { return B >= HSRLE_MIN_BLOCK_SIZE && B <= HSRLE_MAX_BLOCK_SIZE && (B % 128u) == 0; }
+constexpr uint64_t block_count(uint64_t U, uint32_t B) { return (U + B - 1) / B; }
+// a null pointer beats an info that does not describe a container ...
+constexpr int decode_info_check(const void *dContainer, const hsrle_container_info_t *info, const void *dOut)
+{
+  if (dContainer == nullptr || info == nullptr || dOut == nullptr) return HSRLE_ERR_ARGUMENT;
+  const bool ok = info->codec < (uint32_t)kCodecCount && valid_block_size(info->blockSize) && info->blockCount == block_count(info->uncompressedSize, info->blockSize);
+  return ok ? HSRLE_OK : HSRLE_ERR_FORMAT;
+}
+// ... which beats a block range outside it, which beats an output buffer that does not hold the whole container
+constexpr int decode_range_check(const hsrle_container_info_t &info, uint32_t first, uint32_t count, uint64_t cap)
+{
+  return (uint64_t)first + count > info.blockCount ? HSRLE_ERR_ARGUMENT : (cap < info.uncompressedSize ? HSRLE_ERR_CAPACITY : HSRLE_OK);
 }
 
 } // namespace hsrle

@@ -13,7 +13,7 @@ constexpr int kS = HSRLE_S;
 
 // Decode: launch_decode_codec (hsrle_launch.h) by the rule of hsrle_codecs.h (decode_variant) -- the row says whether the width has a 64-byte stream ring.
 
-// Round 6: every codec of 2 .. 8 byte symbols except Greedy is position-parallel for blocks up to 4 KiB (hsrle_capi_container.h: pp_applies) -- the run list encoders of
+// Round 6: every codec of 2 .. 8 byte symbols except Greedy is position-parallel for blocks up to 4 KiB (hsrle_codecs.h: encode_choice) -- the run list encoders of
 // these widths (small containers of 1 .. 4 KiB blocks, and big containers of 3 / 4 byte symbols on run-distributed data) had nothing left to take and are gone.
 // What is launched here: blocks above 4 KiB.
 // 2 byte symbols: the history ring is chosen per input (launch_encode_ring, hsrle_launch.h); wider ones always use 128 bytes.  A/B builds: HSRLE_ENCODE_V1 selects the

@@ -280,13 +280,6 @@ inline hipError_t launch_decode_codec(const DecodeArgs &a, hipStream_t st)
   return launch_decode_case<C, false, false, false>(a, st);
 }
 
-// rle8_multi / rle8_packed_multi: which containers the run list encoder takes (hsrle_encode8r.hip.h; force: 1 always, 2 never -- experiment builds)
-inline bool run_list_applies(uint64_t nBlocks, uint32_t B, uint64_t U, uint32_t force = 0u)
-{
-  if (B < 1024u || B > 4096u || U < 1024u || force == 2u) return false;
-  return force == 1u || nBlocks < 131072u;
-}
-
 // blocks per wave: all of a small container's waves resident at once.  How many waves of a kernel a CU holds is asked once per kernel
 // (LDS and registers decide: 7 .. 10 for the run list encoders) and remembered in a small table; racing first calls write the same value.
 inline uint32_t run_list_waves_per_cu(const void *kernel, hipStream_t st)

@@ -509,6 +509,8 @@ int hsrle_experiments_enabled(void);
 /* round 6: ... and, with blocks ABOVE 4 KiB walked in 4 KiB windows (a wave per block, then a wave per window: csrc/hsrle_encode8pw.hip.h, hsrle_encodeSpw.hip.h,
  * hsrle_encodeLpw.hip.h): rle8_multi / rle8_packed_multi and the plain / Packed codecs of 2 .. 8 byte symbols with blocks of any size; every LUT codec and the
  * position-parallel Short codecs with blocks below 1 MiB: 86 codecs (not: the 8 bit Single codecs, the 128 bit codecs) */
+/* The answer is that of a workspace sized by hsrle_compress_workspace_size (no split regions for blocks of 1 .. 4 KiB): the library's own scratch and a workspace of
+ * hsrle_compress_workspace_size_codec send the small containers of the Greedy codecs with a one-symbol list to HSRLE_PATH_SPLIT where this says HSRLE_PATH_RING. */
 int hsrle_encode_path(int codec, uint64_t uncompressedSize, uint32_t blockSize);
 
 /* Which stream ring (bytes per lane in LDS: 64 or 128) the block decoder of hsrle_decompress_dev_async / hsrle_decompress_blocks_dev_async takes for a
