@@ -33,6 +33,7 @@
 using namespace hsrle;
 
 #include "hsrle_capi_mmtf.h"                // the mmtf / bitmmtf transforms and rle8_mmtf128: plans, their C ABI, their host-pointer functions
+#include "hsrle_capi_sh.h"                  // rle8_sh, both directions: plans, C ABI, host-pointer functions
 
 extern "C" {
 

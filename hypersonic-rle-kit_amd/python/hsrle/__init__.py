@@ -189,6 +189,18 @@ def _lib():
     L.hsrle_rle8_mmtf128_decompress_dev_async.argtypes = [vp, u64, vp, u64, vp, vp, u64, vp]
     L.hsrle_rle8_mmtf_tuning.restype = None
     L.hsrle_rle8_mmtf_tuning.argtypes = [u32]
+    L.rle8_sh_bounds.restype = u32
+    L.rle8_sh_bounds.argtypes = [u32]
+    L.hsrle_rle8_sh_workspace_size.restype = u64
+    L.hsrle_rle8_sh_workspace_size.argtypes = [ci, u64]
+    L.hsrle_rle8_sh_capacity.restype = u64
+    L.hsrle_rle8_sh_capacity.argtypes = [u64]
+    L.hsrle_rle8_sh_compress_dev_async.restype = ci
+    L.hsrle_rle8_sh_compress_dev_async.argtypes = [vp, u64, vp, u64, vp, vp, vp, u64, vp]
+    L.hsrle_rle8_sh_decompress_dev_async.restype = ci
+    L.hsrle_rle8_sh_decompress_dev_async.argtypes = [vp, u64, vp, u64, vp, vp, u64, vp]
+    L.hsrle_rle8_sh_tuning.restype = None
+    L.hsrle_rle8_sh_tuning.argtypes = [u32, u32, u32]
     _LIB = L
     return L
 
@@ -872,3 +884,73 @@ def rle8_mmtf128_decompress_dev(src, dst, status, ws, stream=None):
                                                         ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(stream))
     if rc != OK:
         raise HsrleError(rc, "hsrle_rle8_mmtf128_decompress_dev_async")
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# rle8_sh: run-length coding with a bit stream of capped unary tokens (include/hsrle.h section 5; reference: src/rle_sh.c)
+
+RLE8_SH_DONE, RLE8_SH_MALFORMED, RLE8_SH_CAPACITY = 0, 1, 2
+
+
+def rle8_sh_bounds(n):
+    return int(_lib().rle8_sh_bounds(n))
+
+
+def rle8_sh_capacity(n):
+    """hsrle_rle8_sh_capacity: an output capacity that always suffices for `n` input bytes (include/hsrle.h has the derivation)."""
+    return int(_lib().hsrle_rle8_sh_capacity(n))
+
+
+def rle8_sh_compress(data, out_cap=None):
+    """The reference-named host-pointer function: returns (return value, stream[:return value]).  out_cap defaults to rle8_sh_capacity (the
+    reference's bound is not one, include/hsrle.h)."""
+    data = bytes(data)
+    return call_dropin("rle8_sh_compress", data, rle8_sh_capacity(len(data)) if out_cap is None else out_cap)
+
+
+def rle8_sh_decompress(stream, out_cap):
+    """The reference-named host-pointer function: returns (return value, output[:return value])."""
+    return call_dropin("rle8_sh_decompress", bytes(stream), out_cap)
+
+
+def rle8_sh_workspace_size(decode, size):
+    """hsrle_rle8_sh_workspace_size: bytes of device workspace for `size` uncompressed bytes (0: size == 0 or above 2^30)."""
+    return int(_lib().hsrle_rle8_sh_workspace_size(1 if decode else 0, size))
+
+
+def rle8_sh_tuning(stretch_symbols=0, walk_window=0, serial_state=0):
+    """hsrle_rle8_sh_tuning: symbols per stretch record (1 .. 4096; 0 = 128; a record is never cut inside a word of the bit stream, so below 64
+    every word is a record of its own, of up to 64 symbols), bytes per walk window (64 .. 1024; 0 = 1024), serial_state != 0: the decoder's serial
+    symbol pass instead of the scan under the guess.  Process-global, for tests."""
+    _lib().hsrle_rle8_sh_tuning(stretch_symbols, walk_window, serial_state)
+
+
+def rle8_sh_decode_words(ws):
+    """(fallback ran, stretches whose proof failed) of the last decompress call on the workspace tensor `ws` (include/hsrle.h)."""
+    base = (-ws.data_ptr()) % 256
+    w = ws[base + 8 : base + 16].cpu().numpy().view("<u4")
+    return int(w[0]), int(w[1])
+
+
+def rle8_sh_compress_dev(src, dst, out_size, status, ws, stream=None):
+    """hsrle_rle8_sh_compress_dev_async: enqueue the compression of the CUDA uint8 tensor `src` into `dst` (>= src.numel() + 8 bytes;
+    rle8_sh_capacity(src.numel()) always suffices).  out_size / status: CUDA int32 tensors of one element, they receive the stream size and
+    RLE8_SH_DONE / RLE8_SH_CAPACITY."""
+    for t, what in ((src, "src"), (dst, "dst"), (ws, "ws")):
+        _check_u8_cuda(t, what)
+    rc = _lib().hsrle_rle8_sh_compress_dev_async(ctypes.c_void_p(src.data_ptr()), src.numel(), ctypes.c_void_p(dst.data_ptr()), dst.numel(),
+                                                 ctypes.c_void_p(out_size.data_ptr()), ctypes.c_void_p(status.data_ptr()),
+                                                 ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(stream))
+    if rc != OK:
+        raise HsrleError(rc, "hsrle_rle8_sh_compress_dev_async")
+
+
+def rle8_sh_decompress_dev(src, dst, status, ws, stream=None):
+    """hsrle_rle8_sh_decompress_dev_async: enqueue the decompression of the stream in the CUDA uint8 tensor `src` into `dst`, whose numel() is the
+    uncompressed size.  status: CUDA int32 tensor of one element, receives RLE8_SH_DONE / RLE8_SH_MALFORMED."""
+    for t, what in ((src, "src"), (dst, "dst"), (ws, "ws")):
+        _check_u8_cuda(t, what)
+    rc = _lib().hsrle_rle8_sh_decompress_dev_async(ctypes.c_void_p(src.data_ptr()), src.numel(), ctypes.c_void_p(dst.data_ptr()), dst.numel(),
+                                                   ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(stream))
+    if rc != OK:
+        raise HsrleError(rc, "hsrle_rle8_sh_decompress_dev_async")

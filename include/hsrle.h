@@ -607,8 +607,8 @@ int hsrle_rle8m_decompress_dev_async(const void *dStream, const hsrle_rle8m_info
 /* inSize % 16 (32) bytes behind the last whole row are looked up without an update.  bitmmtf8 / bitmmtf16: XOR with the previous byte /  */
 /* little-endian 16 bit word (an odd last byte of bitmmtf16 is copied).  Same names, arguments and return values as the reference: inSize */
 /* on success, 0 for inSize == 0, inSize > outSize, a NULL pointer or no usable device.  Host pointers, staged per device like section 1. */
-/* rle8_mmtf128_* (RLE + MMTF + bit packing, rle.h:442-452) follows below.  Still open of rle.h: rle8_sh_*, and rle8_mmtf256_compress /    */
-/* _decompress, which the reference declares and never defines.                                                                            */
+/* rle8_mmtf128_* (RLE + MMTF + bit packing, rle.h:442-452) and rle8_sh_* (rle.h:455-458) follow below.  Still open of rle.h: only          */
+/* rle8_mmtf256_compress / _decompress, which the reference declares and never defines.                                                    */
 uint32_t mmtf_bounds(const uint32_t inSize);
 uint32_t mmtf128_encode(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize);
 uint32_t mmtf128_decode(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize);
@@ -688,6 +688,76 @@ int hsrle_rle8_mmtf128_compress_dev_async(const void *dIn, uint64_t inSize, void
 int hsrle_rle8_mmtf128_decompress_dev_async(const void *dStream, uint64_t streamSize, void *dOut, uint64_t outSize, uint32_t *dStatus, void *dWorkspace, uint64_t workspaceSize,
                                             void *stream);
 void hsrle_rle8_mmtf_tuning(uint32_t spanRows);
+
+/*
+ * rle8_sh (src/rle_sh.c, rle.h:455-458): run-length coding with a bit stream of capped unary tokens -- one stream: u32 inSize, u32 streamSize, a body
+ * of whole bytes upward from offset 8, the token bits downward from the last byte (csrc/hsrle_rle8sh.hip.h has the grammar).  Same names, arguments and
+ * return values as the reference; the streams are the reference's byte for byte.
+ * bounds: 0 above 2^30, else size + 13, the reference's value.  It is NOT an upper bound of the stream: random bytes of n >= 8 give n + 18 (the
+ * reference's own test is outSize >= n + 8, and with a buffer of exactly n + 13 its bit stream and its body run into each other).
+ * compress: the stream's size; 0 for a NULL pointer, inSize == 0, outSize < inSize + 8 (the reference's test).
+ * decompress: the header's inSize; 0 for a NULL pointer, a zero size, header sizes larger than the arguments.  Where this library differs, on purpose:
+ *  - compress returns 0 for inSize > 2^30, and 0 when the stream does not fit in outSize: it never writes past outSize.
+ *  - A CAPACITY THAT ALWAYS SUFFICES is hsrle_rle8_sh_capacity(n) = n + n / 221 + 21.  Derivation: the encoder cuts the input into blocks, each ended
+ *    by an EVENT -- a run of >= 10 equal bytes that becomes the new R (7 bits + 5 bytes for >= 10 bytes: at least 4.125 bytes saved) or a run of >= 15
+ *    bytes of R (a FILL: more saved).  What a block costs beyond its own bytes:
+ *      raw COPY large  4.875 (7 bits + u32), only for >= 263 bytes; with its event at most + 0.75 per 273 bytes = 1 / 364 per byte
+ *      raw COPY small  1.875, under 7 bytes coded as symbols at most 1.5 (a literal is 2 bits + its byte): both less than the event saves
+ *      encoded copy    the 7 : 2 rule (7 r > 2 o for r bytes of R and o others) admits a span whose symbols cost r / 8 + 1.25 o < r + o, but with a
+ *                      margin that can be next to nothing, and the span is cut into BLOCKS OF 416 that cost 7 bits + 1 byte each; the last block may
+ *                      be as short as 162, so a span of c bytes has at most (c - 162) / 416 + 1 blocks: 1.875 (c + 254) / 416 = c / 221.9 + 1.145.
+ *                      THIS is the worst case per byte; with its event 1.875 c / 416 - 2.98 < c / 221.
+ *    So every block with its event grows by less than (its bytes) / 221.  The last block has no event: at most 4.875, or c / 221.9 + 1.145.  The
+ *    terminator is 4.875, the header 8, the bit stream is rounded up to a byte (< 1), n / 221 is rounded down (< 1): 8 + 4.875 + 4.875 + 2 < 21.
+ *    tests/test_gpu_rle8_sh.py and tests/test_rle8_sh_model.py hold it against random bytes, raw blocks of 263 bytes between runs of 10, and long
+ *    spans that the 7 : 2 rule admits by one byte.
+ *  - decompress checks EVERY token BEFORE anything is written and returns 0 for a malformed stream: a stream shorter than 13 bytes (header, the
+ *    terminator's u32, one bit byte) or a header inSize of 0 or above 2^30; a body cursor that reaches a byte whose bits were consumed, or bits that
+ *    reach a consumed body byte (a missing terminator and an encoded copy whose bits run out end here); a token whose output would pass inSize; any
+ *    token but the terminator behind the last output byte (a FILL of no bytes too); a terminator with output missing.  The reference checks nothing.
+ *  - Everything else decodes as the reference does: a literal equal to second / third / lastOccurred, FILL large counts through the 32-bit wrap
+ *    (a stored 0xFFFFFFF2 .. 0xFFFFFFFF is a count of 0 .. 13), a gap between body and bits.
+ * Host pointers, staged per device like the functions above.
+ */
+uint32_t rle8_sh_bounds(const uint32_t size);
+uint32_t rle8_sh_compress(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize);
+uint32_t rle8_sh_decompress(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize);
+
+/*
+ * The same, device resident and ENQUEUE-ONLY (nothing allocates, synchronises or reads device memory; a HIP graph can capture the calls; what has to
+ * be zero is zeroed by a kernel, every other word the kernels read is written by a kernel before).  Buffers at any byte address, not overlapping;
+ * dOutSize / dStatus: device words, 4-byte aligned.  dWorkspace >= hsrle_rle8_sh_workspace_size(decode, uncompressed size) bytes, contents do not matter.
+ * compress: 1 <= inSize <= 2^30 and outCapacity >= inSize + 8, else HSRLE_ERR_ARGUMENT / HSRLE_ERR_CAPACITY and nothing is enqueued.  *dOutSize
+ *   receives the stream's size and *dStatus HSRLE_RLE8_SH_DONE, or 0 and HSRLE_RLE8_SH_CAPACITY when the stream is larger than outCapacity (then
+ *   nothing is written to dOut; hsrle_rle8_sh_capacity(inSize) suffices for every input; 0 for inSize == 0 or above 2^30).  Workspace: an item per decision
+ *   (size / 5), an emission record per item and per block of an encoded copy, the bit stream before it is placed: about 11 bytes per input byte.
+ *   ONE wave decides run by run and ONE lane follows second / third / lastOccurred through the bytes of the symbol stretches; the
+ *   bytes of raw COPYs and FILLs are touched by whole waves only.
+ * decompress: outSize is the UNCOMPRESSED size, which the caller knows (the stream's first word), 1 .. 2^30.  The header is read on the device;
+ *   *dStatus receives HSRLE_RLE8_SH_DONE, or HSRLE_RLE8_SH_MALFORMED (header inSize != outSize, header streamSize > streamSize, or a chain as
+ *   described above); then NOTHING has been written to dOut.  Never more than outSize bytes are written.  Workspace: a record of 16 bytes and 8 bytes
+ *   of summary and state per FILL, raw COPY and stretch of symbol tokens.  A record holds at least one output byte and a hand-made stream can hold
+ *   one per byte, so the size is 24 bytes per output byte (a stream from the encoder uses under a fifth of the records).
+ *   ONE wave tokenises the stream (the format's first serial dependence).  second / third / lastOccurred, the second: a lane per stretch sums up its
+ *   own tokens, one workgroup scans the SUMMARIES (a run of records per thread) under the guess that no literal behind S / T promotes -- true of
+ *   every stream the encoder writes -- and every expanding lane proves the guess for its stretch.  A failed proof sets a device word that gates the
+ *   fallback inside the same call: one lane follows the state through every L / S / T token and the stretches are expanded again.
+ *   For tests and measurements: behind the call, word 2 of the workspace (from its 256-byte aligned start) is 1 if the fallback ran, word 3 the
+ *   number of stretches whose proof failed.
+ * hsrle_rle8_sh_tuning: symbols per stretch record of the decoder (1 .. 4096; 0 or above 4096 = 128; a record is never cut inside a word of the bit
+ * stream, so below 64 every word is a record of its own, of up to 64 symbols), bytes per window of its walk (64 .. 1024 in steps of 16; anything
+ * else = 1024), and serialState != 0: the fallback instead of the scan, always.  Any value gives the same bytes.  PROCESS-GLOBAL, for tests.
+ */
+#define HSRLE_RLE8_SH_DONE 0
+#define HSRLE_RLE8_SH_MALFORMED 1
+#define HSRLE_RLE8_SH_CAPACITY 2
+uint64_t hsrle_rle8_sh_workspace_size(int decode, uint64_t size);
+uint64_t hsrle_rle8_sh_capacity(uint64_t inSize);
+int hsrle_rle8_sh_compress_dev_async(const void *dIn, uint64_t inSize, void *dOut, uint64_t outCapacity, uint32_t *dOutSize, uint32_t *dStatus, void *dWorkspace,
+                                     uint64_t workspaceSize, void *stream);
+int hsrle_rle8_sh_decompress_dev_async(const void *dStream, uint64_t streamSize, void *dOut, uint64_t outSize, uint32_t *dStatus, void *dWorkspace, uint64_t workspaceSize,
+                                       void *stream);
+void hsrle_rle8_sh_tuning(uint32_t stretchSymbols, uint32_t walkWindow, uint32_t serialState);
 
 int hsrle_kernel_waves_per_cu(int codec, int decode);
 const char *hsrle_version(void);

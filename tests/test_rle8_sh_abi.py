@@ -1,0 +1,144 @@
+"""The rle8_sh exports without a GPU: the reference's names (src/rle.h:455-458), the library's own device entry points, the bounds, the capacity
+that always suffices, and every return value that is decided on the host before a device is touched.  rle8_mmtf256_compress / _decompress (declared
+by the reference, defined nowhere) stay unexported."""
+import ctypes
+import os
+
+import pytest
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(REPO, "hypersonic-rle-kit_amd", "libhsrle_hip.so")
+
+REFERENCE_NAMES = ["rle8_sh_bounds", "rle8_sh_compress", "rle8_sh_decompress"]
+OWN_NAMES = ["hsrle_rle8_sh_workspace_size", "hsrle_rle8_sh_capacity", "hsrle_rle8_sh_compress_dev_async", "hsrle_rle8_sh_decompress_dev_async", "hsrle_rle8_sh_tuning"]
+NEVER_DEFINED = ["rle8_mmtf256_compress", "rle8_mmtf256_decompress"]
+OK, ERR_ARGUMENT, ERR_CAPACITY = 0, 1, 2
+MAX_IN = 1 << 30
+
+
+@pytest.fixture(scope="module")
+def lib():
+    if not os.path.exists(LIB):
+        import subprocess
+
+        subprocess.check_call(["make", "-s", "-j8", "-C", os.path.join(REPO, "hypersonic-rle-kit_amd")])
+    L = ctypes.CDLL(LIB)
+    vp, u32, u64, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
+    L.rle8_sh_bounds.restype = u32
+    L.rle8_sh_bounds.argtypes = [u32]
+    for nm in REFERENCE_NAMES[1:]:
+        getattr(L, nm).restype = u32
+        getattr(L, nm).argtypes = [vp, u32, vp, u32]
+    L.hsrle_rle8_sh_workspace_size.restype = u64
+    L.hsrle_rle8_sh_workspace_size.argtypes = [ci, u64]
+    L.hsrle_rle8_sh_capacity.restype = u64
+    L.hsrle_rle8_sh_capacity.argtypes = [u64]
+    L.hsrle_rle8_sh_compress_dev_async.restype = ci
+    L.hsrle_rle8_sh_compress_dev_async.argtypes = [vp, u64, vp, u64, vp, vp, vp, u64, vp]
+    L.hsrle_rle8_sh_decompress_dev_async.restype = ci
+    L.hsrle_rle8_sh_decompress_dev_async.argtypes = [vp, u64, vp, u64, vp, vp, u64, vp]
+    L.hsrle_rle8_sh_tuning.restype = None
+    L.hsrle_rle8_sh_tuning.argtypes = [u32, u32, u32]
+    L.hsrle_rle8_sh_tuning(0, 0, 0)
+    return L
+
+
+def test_names_are_exported(lib):
+    for nm in REFERENCE_NAMES + OWN_NAMES:
+        assert hasattr(lib, nm), nm
+    for nm in NEVER_DEFINED:
+        assert not hasattr(lib, nm), f"{nm} has no body in the reference and must not be exported"
+
+
+def test_bounds(lib):
+    assert lib.rle8_sh_bounds(0) == 13
+    assert lib.rle8_sh_bounds(1) == 14
+    assert lib.rle8_sh_bounds(MAX_IN) == MAX_IN + 13
+    assert lib.rle8_sh_bounds(MAX_IN + 1) == 0
+
+
+def test_capacity(lib):
+    assert lib.hsrle_rle8_sh_capacity(0) == 0 and lib.hsrle_rle8_sh_capacity(MAX_IN + 1) == 0
+    for n in (1, 8, 220, 221, 100000, MAX_IN):
+        assert lib.hsrle_rle8_sh_capacity(n) == n + n // 221 + 21
+    assert lib.hsrle_rle8_sh_capacity(1000) >= 1000 + 18                     # random bytes: n + 18
+
+
+def test_workspace_size(lib):
+    for decode in (0, 1):
+        assert lib.hsrle_rle8_sh_workspace_size(decode, 0) == 0
+        assert lib.hsrle_rle8_sh_workspace_size(decode, MAX_IN + 1) == 0
+        last = 0
+        for n in (1, 15, 16, 4096, 1 << 20, MAX_IN):
+            size = lib.hsrle_rle8_sh_workspace_size(decode, n)
+            assert size >= last and size > n                                 # monotone
+            last = size
+    # compress: an item per 5 bytes (16), an emission record per item and per 256 bytes (32), the bit buffer (under a byte per byte)
+    assert lib.hsrle_rle8_sh_workspace_size(0, MAX_IN) <= 11 * MAX_IN + (1 << 20)
+    # decompress: a record (16) and summary / state (8) per output byte
+    assert lib.hsrle_rle8_sh_workspace_size(1, MAX_IN) <= 24 * MAX_IN + (1 << 20)
+
+
+def test_tuning_does_not_change_the_workspace(lib):
+    try:
+        base = lib.hsrle_rle8_sh_workspace_size(1, 1 << 20)
+        for stretch, window, serial in ((1, 64, 0), (4096, 1008, 1), (5000, 32, 0), (7, 2048, 1)):
+            lib.hsrle_rle8_sh_tuning(stretch, window, serial)
+            assert lib.hsrle_rle8_sh_workspace_size(1, 1 << 20) == base
+    finally:
+        lib.hsrle_rle8_sh_tuning(0, 0, 0)
+
+
+def test_host_decided_return_values_of_the_reference_names(lib):
+    src, dst = ctypes.create_string_buffer(256), ctypes.create_string_buffer(256)
+    a, b = ctypes.addressof(src), ctypes.addressof(dst)
+    assert lib.rle8_sh_compress(None, 32, b, 256) == 0
+    assert lib.rle8_sh_compress(a, 32, None, 256) == 0
+    assert lib.rle8_sh_compress(a, 0, b, 256) == 0
+    assert lib.rle8_sh_compress(a, 32, b, 39) == 0                           # outSize < inSize + 8, the reference's own test
+    assert lib.rle8_sh_compress(a, MAX_IN + 1, b, 0xFFFFFFFF) == 0
+    assert lib.rle8_sh_decompress(None, 32, b, 256) == 0
+    assert lib.rle8_sh_decompress(a, 32, None, 256) == 0
+    assert lib.rle8_sh_decompress(a, 0, b, 256) == 0
+    assert lib.rle8_sh_decompress(a, 32, b, 0) == 0
+    ctypes.memmove(a, (ctypes.c_uint32 * 2)(100, 20), 8)                     # header: inSize 100, streamSize 20
+    assert lib.rle8_sh_decompress(a, 32, b, 99) == 0                         # header inSize > outSize
+    assert lib.rle8_sh_decompress(a, 19, b, 256) == 0                        # header streamSize > inSize
+    ctypes.memmove(a, (ctypes.c_uint32 * 2)(100, 12), 8)                     # a stream shorter than header + terminator + one bit byte
+    assert lib.rle8_sh_decompress(a, 32, b, 256) == 0
+    ctypes.memmove(a, (ctypes.c_uint32 * 2)(0, 20), 8)                       # header inSize 0
+    assert lib.rle8_sh_decompress(a, 32, b, 256) == 0
+    assert dst.raw == bytes(256)
+
+
+def test_dev_async_argument_checks(lib):
+    # host buffers stand in for device pointers: every call below is refused on the host, before anything could touch them
+    src, dst, ws, words = ctypes.create_string_buffer(4096), ctypes.create_string_buffer(4096), ctypes.create_string_buffer(64), ctypes.create_string_buffer(16)
+    a, b, w, s = ctypes.addressof(src), ctypes.addressof(dst), ctypes.addressof(ws), (ctypes.addressof(words) + 3) & ~3
+    big = 1 << 40
+    C, D = lib.hsrle_rle8_sh_compress_dev_async, lib.hsrle_rle8_sh_decompress_dev_async
+    need = lib.hsrle_rle8_sh_workspace_size(0, 1024)
+    assert C(None, 1024, b, 2048, s, s + 4, w, big, None) == ERR_ARGUMENT
+    assert C(a, 1024, None, 2048, s, s + 4, w, big, None) == ERR_ARGUMENT
+    assert C(a, 1024, b, 2048, None, s + 4, w, big, None) == ERR_ARGUMENT
+    assert C(a, 1024, b, 2048, s, None, w, big, None) == ERR_ARGUMENT
+    assert C(a, 1024, b, 2048, s, s + 4, None, big, None) == ERR_ARGUMENT
+    assert C(a, 0, b, 2048, s, s + 4, w, big, None) == ERR_ARGUMENT
+    assert C(a, MAX_IN + 1, b, big, s, s + 4, w, big, None) == ERR_ARGUMENT
+    assert C(a, 1024, a + 1000, 2048, s, s + 4, w, big, None) == ERR_ARGUMENT           # overlap
+    assert C(a, 1024, b, 2048, s + 1, s + 4, w, big, None) == ERR_ARGUMENT             # unaligned size word
+    assert C(a, 1024, b, 2048, s, s + 6, w, big, None) == ERR_ARGUMENT                 # unaligned status word
+    assert C(a, 1024, b, 1024 + 7, s, s + 4, w, big, None) == ERR_CAPACITY             # outCapacity < inSize + 8
+    assert C(a, 1024, b, 2048, s, s + 4, w, need - 1, None) == ERR_CAPACITY
+    need = lib.hsrle_rle8_sh_workspace_size(1, 1024)
+    assert D(None, 100, b, 1024, s, w, big, None) == ERR_ARGUMENT
+    assert D(a, 100, None, 1024, s, w, big, None) == ERR_ARGUMENT
+    assert D(a, 100, b, 1024, None, w, big, None) == ERR_ARGUMENT
+    assert D(a, 100, b, 1024, s, None, big, None) == ERR_ARGUMENT
+    assert D(a, 0, b, 1024, s, w, big, None) == ERR_ARGUMENT
+    assert D(a, 100, b, 0, s, w, big, None) == ERR_ARGUMENT
+    assert D(a, 100, b, MAX_IN + 1, s, w, big, None) == ERR_ARGUMENT
+    assert D(a, 100, a + 50, 1024, s, w, big, None) == ERR_ARGUMENT                    # overlap
+    assert D(a, 100, b, 1024, s + 2, w, big, None) == ERR_ARGUMENT
+    assert D(a, 100, b, 1024, s, w, need - 1, None) == ERR_CAPACITY
+    assert dst.raw == bytes(4096)
