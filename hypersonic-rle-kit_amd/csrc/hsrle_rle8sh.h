@@ -28,4 +28,20 @@ struct ShEncPlan
 hipError_t rle8sh_compress_enqueue(const ShEncPlan &p, const uint8_t *dIn, uint8_t *dOut, uint32_t outCap, uint32_t *dOutSize, uint32_t *dStatus, uint8_t *ws, hipStream_t st);
 hipError_t rle8sh_decompress_enqueue(const ShPlan &p, const uint8_t *dStream, uint32_t streamCap, uint8_t *dOut, uint32_t *dStatus, uint8_t *ws, hipStream_t st);
 
+// The blocked form (hsrle_capi_shb.h plans, inst_rle8shb.hip launches, kernels: hsrle_rle8shb.hip.h).  Workspace, from its 256-byte aligned start: 256 bytes
+// of words for the whole call, then `inFlight` SLOTS, each the workspace of a single stream of blockSize bytes (enc.total / dec.total).
+struct ShbPlan
+{
+  uint64_t size = 0;                // uncompressed bytes of the whole container
+  uint32_t blockSize = 0, blockCount = 0;
+  uint32_t inFlight = 0;            // blocks per group: min(blocks of the call, blocks in flight)
+  ShEncPlan enc;                    // of ONE block
+  ShPlan dec;
+  uint64_t total = 0;
+};
+
+hipError_t rle8shb_compress_enqueue(const ShbPlan &p, const uint8_t *dIn, uint8_t *dOut, uint64_t outCap, uint64_t *dOutSize, uint32_t *dStatus, uint8_t *ws, hipStream_t st);
+hipError_t rle8shb_decompress_enqueue(const ShbPlan &p, const uint8_t *dContainer, uint64_t payloadSize, uint32_t firstBlock, uint32_t blockCount, uint8_t *dOut,
+                                      uint32_t *dStatus, uint8_t *ws, hipStream_t st);
+
 }   // namespace hsrle

@@ -89,8 +89,9 @@ __device__ __forceinline__ uint64_t sh_bits64(const uint8_t *stream, uint32_t S,
   return s ? (lo >> s) | (nxt << (64u - s)) : lo;
 }
 
-template <int UNUSED = 0>
-__global__ __launch_bounds__(64) void k_sh_walk(ShDecArgs a)
+// The passes are __device__ functions of one argument block (and, where a lane has an index of its own, that index), so that the kernels of ONE
+// stream below and the kernels of the blocked form (hsrle_rle8shb.hip.h: a workgroup that finds its own block) run the same code.
+__device__ __forceinline__ void d_sh_walk(const ShDecArgs &a)
 {
   __shared__ __attribute__((aligned(16))) uint64_t sBits[kShWinMax / 8u + 2u];
   __shared__ __attribute__((aligned(16))) uint8_t sBody[kShWinMax];
@@ -237,6 +238,8 @@ __global__ __launch_bounds__(64) void k_sh_walk(ShDecArgs a)
     *a.status = status;
   }
 }
+template <int UNUSED = 0>
+__global__ __launch_bounds__(64) void k_sh_walk(ShDecArgs a) { d_sh_walk(a); }
 
 // Summary of a stretch, from its own tokens alone (a lane per stretch record): kind and value of its first and last token that is not Z
 // (0 none, 1 L, 2 S, 3 T) and its SURE promotions -- a literal equal to the literal right in front of it -- of which the last two matter.
@@ -375,8 +378,7 @@ __global__ __launch_bounds__(1024) void k_sh_scan(ShDecArgs a)
 
 // THE FALLBACK, and the simplest correct decoder of the symbol state: one lane, every stretch in order.  Zero bits are skipped by count, so the
 // cost is per L / S / T token.  It runs when a proof of k_sh_expand_sym<0> failed or when hsrle_rle8_sh_tuning forces it.
-template <int UNUSED = 0>
-__global__ __launch_bounds__(64) void k_sh_state(ShDecArgs a)
+__device__ __forceinline__ void d_sh_state(const ShDecArgs &a)
 {
   if (threadIdx.x != 0u || a.ctrl[0] != kShDone || a.ctrl[2] == 0u) return;
   const uint32_t n = a.ctrl[1], S = ld32(a.stream + 4);
@@ -429,12 +431,14 @@ __global__ __launch_bounds__(64) void k_sh_state(ShDecArgs a)
     }
   }
 }
-
 template <int UNUSED = 0>
-__global__ __launch_bounds__(256) void k_sh_expand_blocks(ShDecArgs a)
+__global__ __launch_bounds__(64) void k_sh_state(ShDecArgs a) { d_sh_state(a); }
+
+// `lane`: the 16 output bytes [16 lane, 16 lane + 16)
+__device__ __forceinline__ void d_sh_expand_blocks(const ShDecArgs &a, uint64_t lane)
 {
   if (a.ctrl[0] != kShDone) return;
-  const uint64_t c64 = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 16u;
+  const uint64_t c64 = lane * 16u;
   if (c64 >= a.size) return;
   const uint32_t c0 = (uint32_t)c64, c1 = umin(a.size - c0, 16u) + c0, n = a.ctrl[1];
   uint32_t lo = 0u, hi = n;   // (record 0 starts at output offset 0, the offsets rise strictly)
@@ -465,16 +469,17 @@ __global__ __launch_bounds__(256) void k_sh_expand_blocks(ShDecArgs a)
     }
   }
 }
+template <int UNUSED = 0>
+__global__ __launch_bounds__(256) void k_sh_expand_blocks(ShDecArgs a) { d_sh_expand_blocks(a, (uint64_t)blockIdx.x * 256u + threadIdx.x); }
 
 // PASS 0: from the scan's states; every lane PROVES the guess for its stretch: the state it ends in must be the state the scan gave the next
 // record.  If that holds for every stretch, every state of the scan is the true one (by induction from the first); if not, ctrl[2] gates the
 // fallback.  PASS 1: again, from the serial pass's states, only when ctrl[2] is set.
 template <int PASS>
-__global__ __launch_bounds__(256) void k_sh_expand_sym(ShDecArgs a)
+__device__ __forceinline__ void d_sh_expand_sym(const ShDecArgs &a, uint32_t i)
 {
   if (a.ctrl[0] != kShDone) return;
   if (PASS == 0 ? a.force != 0u : a.ctrl[2] == 0u) return;
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= a.ctrl[1]) return;
   const uint4 q = a.rec[i];
   const uint32_t kind = q.w & 3u;
@@ -512,6 +517,8 @@ __global__ __launch_bounds__(256) void k_sh_expand_sym(ShDecArgs a)
     atomicAdd(&a.ctrl[3], 1u);
   }
 }
+template <int PASS>
+__global__ __launch_bounds__(256) void k_sh_expand_sym(ShDecArgs a) { d_sh_expand_sym<PASS>(a, blockIdx.x * 256u + threadIdx.x); }
 
 // ------------------------------------------------------------------------------------------------------------------
 // encode
@@ -541,15 +548,14 @@ struct ShEncArgs
   uint32_t size, maxItems, maxEr, bitWords, outCap;
 };
 
-template <int UNUSED = 0>
-__global__ __launch_bounds__(256) void k_she_zero(ShEncArgs a)
+__device__ __forceinline__ void d_she_zero(const ShEncArgs &a, uint32_t i)
 {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (a.ctrl[0] == 0u && (uint64_t)i * 4u < a.ctrl[4]) a.bits[i] = 0u;   // (only the words the bit stream will fill: k_she_code has counted them)
 }
-
 template <int UNUSED = 0>
-__global__ __launch_bounds__(64) void k_she_decide(ShEncArgs a)
+__global__ __launch_bounds__(256) void k_she_zero(ShEncArgs a) { d_she_zero(a, blockIdx.x * 256u + threadIdx.x); }
+
+__device__ __forceinline__ void d_she_decide(const ShEncArgs &a)
 {
   __shared__ __attribute__((aligned(16))) uint8_t sWin[1024];
   __shared__ __attribute__((aligned(16))) uint64_t sMask[16], sIsR[16];
@@ -683,9 +689,10 @@ __global__ __launch_bounds__(64) void k_she_decide(ShEncArgs a)
     a.ctrl[1] = nItems;
   }
 }
-
 template <int UNUSED = 0>
-__global__ __launch_bounds__(64) void k_she_code(ShEncArgs a)
+__global__ __launch_bounds__(64) void k_she_decide(ShEncArgs a) { d_she_decide(a); }
+
+__device__ __forceinline__ void d_she_code(const ShEncArgs &a)
 {
   if (threadIdx.x != 0u) return;
   const uint32_t n = a.size, nItems = a.ctrl[1];
@@ -766,12 +773,12 @@ __global__ __launch_bounds__(64) void k_she_code(ShEncArgs a)
   *a.outSize = fits ? (uint32_t)total : 0u;
   *a.status = fits ? kShDone : kShCapacity;
 }
-
 template <int UNUSED = 0>
-__global__ __launch_bounds__(256) void k_she_emit(ShEncArgs a)
+__global__ __launch_bounds__(64) void k_she_code(ShEncArgs a) { d_she_code(a); }
+
+__device__ __forceinline__ void d_she_emit(const ShEncArgs &a, uint32_t e)
 {
   if (a.ctrl[0] != 0u) return;
-  const uint32_t e = blockIdx.x * 256u + threadIdx.x;
   if (e >= a.ctrl[2]) return;
   const uint4 q = a.er[2u * e], o = a.er[2u * e + 1u];
   const uint32_t kind = q.z & 0xFFu, R = (q.z >> 8) & 0xFFu, cnt = q.y;
@@ -824,12 +831,14 @@ __global__ __launch_bounds__(256) void k_she_emit(ShEncArgs a)
   }
   if (have != 0u) atomicOr(&a.bits[word], (uint32_t)acc);
 }
-
 template <int UNUSED = 0>
-__global__ __launch_bounds__(256) void k_she_raw(ShEncArgs a)
+__global__ __launch_bounds__(256) void k_she_emit(ShEncArgs a) { d_she_emit(a, blockIdx.x * 256u + threadIdx.x); }
+
+// `lane`: the 16 input bytes [16 lane, 16 lane + 16)
+__device__ __forceinline__ void d_she_raw(const ShEncArgs &a, uint64_t lane)
 {
   if (a.ctrl[0] != 0u) return;
-  const uint64_t c64 = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 16u;
+  const uint64_t c64 = lane * 16u;
   if (c64 >= a.size) return;
   const uint32_t c0 = (uint32_t)c64, c1 = umin(a.size - c0, 16u) + c0, ne = a.ctrl[2];
   uint32_t lo = 0u, hi = ne;   // (record 0 starts at input offset 0, the offsets rise strictly, the last record is the END at `size`)
@@ -849,16 +858,19 @@ __global__ __launch_bounds__(256) void k_she_raw(ShEncArgs a)
     else for (uint32_t k = 0; k < e - s; k++) dst[k] = a.in[s + k];
   }
 }
-
 template <int UNUSED = 0>
-__global__ __launch_bounds__(256) void k_she_place(ShEncArgs a)
+__global__ __launch_bounds__(256) void k_she_raw(ShEncArgs a) { d_she_raw(a, (uint64_t)blockIdx.x * 256u + threadIdx.x); }
+
+__device__ __forceinline__ void d_she_place(const ShEncArgs &a, uint32_t g)
 {
   if (a.ctrl[0] != 0u) return;
-  const uint32_t g = blockIdx.x * 256u + threadIdx.x, total = a.ctrl[3], bitBytes = a.ctrl[4];
+  const uint32_t total = a.ctrl[3], bitBytes = a.ctrl[4];
   if (g == 0u) { st32(a.out, a.size); st32(a.out + 4, total); }
   if ((uint64_t)g * 4u >= bitBytes) return;
   const uint32_t w = a.bits[g];
   for (uint32_t j = 0; j < 4u && g * 4u + j < bitBytes; j++) a.out[total - 1u - (g * 4u + j)] = (uint8_t)(w >> (8u * j));
 }
+template <int UNUSED = 0>
+__global__ __launch_bounds__(256) void k_she_place(ShEncArgs a) { d_she_place(a, blockIdx.x * 256u + threadIdx.x); }
 
 }   // namespace hsrle

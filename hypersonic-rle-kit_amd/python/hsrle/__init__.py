@@ -43,6 +43,22 @@ class ContainerInfo(ctypes.Structure):
         return HEADER_SIZE + 8 * (self.blockCount + 1)
 
 
+class Rle8ShBlocksInfo(ctypes.Structure):
+    """hsrle_rle8_sh_blocks_info_t: the header of an rle8_sh block container."""
+
+    _fields_ = [
+        ("uncompressedSize", ctypes.c_uint64),
+        ("blockSize", ctypes.c_uint32),
+        ("blockCount", ctypes.c_uint32),
+        ("payloadSize", ctypes.c_uint64),
+        ("totalSize", ctypes.c_uint64),
+    ]
+
+    @property
+    def payload_start(self):
+        return HEADER_SIZE + 8 * (self.blockCount + 1)
+
+
 class MonoIndexInfo(ctypes.Structure):
     """hsrle_mono_index_info_t: the header of a persistent index of one monolithic stream."""
 
@@ -201,6 +217,24 @@ def _lib():
     L.hsrle_rle8_sh_decompress_dev_async.argtypes = [vp, u64, vp, u64, vp, vp, u64, vp]
     L.hsrle_rle8_sh_tuning.restype = None
     L.hsrle_rle8_sh_tuning.argtypes = [u32, u32, u32]
+    L.hsrle_rle8_sh_blocks_bound.restype = u64
+    L.hsrle_rle8_sh_blocks_bound.argtypes = [u64, u32]
+    L.hsrle_rle8_sh_blocks_workspace_size.restype = u64
+    L.hsrle_rle8_sh_blocks_workspace_size.argtypes = [ci, u64, u32]
+    L.hsrle_rle8_sh_blocks_info_host.restype = ci
+    L.hsrle_rle8_sh_blocks_info_host.argtypes = [vp, u64, ctypes.POINTER(Rle8ShBlocksInfo)]
+    L.hsrle_rle8_sh_blocks_info_dev.restype = ci
+    L.hsrle_rle8_sh_blocks_info_dev.argtypes = [vp, u64, ctypes.POINTER(Rle8ShBlocksInfo), vp]
+    L.hsrle_rle8_sh_compress_blocks_dev_async.restype = ci
+    L.hsrle_rle8_sh_compress_blocks_dev_async.argtypes = [vp, u64, u32, vp, u64, vp, vp, vp, u64, vp]
+    L.hsrle_rle8_sh_decompress_blocks_dev_async.restype = ci
+    L.hsrle_rle8_sh_decompress_blocks_dev_async.argtypes = [vp, ctypes.POINTER(Rle8ShBlocksInfo), u32, u32, vp, u64, vp, vp, u64, vp]
+    L.hsrle_rle8_sh_compress_blocks_host.restype = ci
+    L.hsrle_rle8_sh_compress_blocks_host.argtypes = [vp, u64, u32, vp, u64, ctypes.POINTER(u64)]
+    L.hsrle_rle8_sh_decompress_blocks_host.restype = ci
+    L.hsrle_rle8_sh_decompress_blocks_host.argtypes = [vp, u64, vp, u64, ctypes.POINTER(u64)]
+    L.hsrle_rle8_sh_blocks_tuning.restype = None
+    L.hsrle_rle8_sh_blocks_tuning.argtypes = [u32]
     _LIB = L
     return L
 
@@ -954,3 +988,83 @@ def rle8_sh_decompress_dev(src, dst, status, ws, stream=None):
                                                    ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(stream))
     if rc != OK:
         raise HsrleError(rc, "hsrle_rle8_sh_decompress_dev_async")
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the rle8_sh block container: many independent rle8_sh streams per call (include/hsrle.h section 5)
+
+def rle8_sh_blocks_bound(n, block_size=0):
+    """hsrle_rle8_sh_blocks_bound: a container capacity that always suffices (0: bad block size, n == 0, too many blocks).  block_size 0 = 4096."""
+    return int(_lib().hsrle_rle8_sh_blocks_bound(n, block_size))
+
+
+def rle8_sh_blocks_workspace_size(decode, n, block_size=0):
+    """hsrle_rle8_sh_blocks_workspace_size: bytes of device workspace; a function of min(blocks, blocks in flight) and the block size."""
+    return int(_lib().hsrle_rle8_sh_blocks_workspace_size(1 if decode else 0, n, block_size))
+
+
+def rle8_sh_blocks_tuning(blocks_in_flight=0):
+    """hsrle_rle8_sh_blocks_tuning: blocks per group (0 = the default).  Any value gives the same bytes.  Process-global, for tests."""
+    _lib().hsrle_rle8_sh_blocks_tuning(blocks_in_flight)
+
+
+def rle8_sh_blocks_info(container):
+    """Rle8ShBlocksInfo of a container in a CUDA tensor (reads the header, synchronises), a CPU tensor or bytes."""
+    info = Rle8ShBlocksInfo()
+    if hasattr(container, "is_cuda"):
+        if container.is_cuda:
+            rc = _lib().hsrle_rle8_sh_blocks_info_dev(ctypes.c_void_p(container.data_ptr()), container.numel(), ctypes.byref(info), _stream_ptr())
+        else:
+            rc = _lib().hsrle_rle8_sh_blocks_info_host(ctypes.c_void_p(container.data_ptr()), container.numel(), ctypes.byref(info))
+    else:
+        b = bytes(container)
+        rc = _lib().hsrle_rle8_sh_blocks_info_host(b, len(b), ctypes.byref(info))
+    if rc != OK:
+        raise HsrleError(rc, "hsrle_rle8_sh_blocks_info")
+    return info
+
+
+def rle8_sh_blocks_compress_dev(src, dst, out_size, status, ws, block_size=0, stream=None):
+    """hsrle_rle8_sh_compress_blocks_dev_async: enqueue the compression of the CUDA uint8 tensor `src` into the container buffer `dst`
+    (rle8_sh_blocks_bound always suffices).  out_size: CUDA int64 tensor of one element, receives the container's size (0: it did not fit);
+    status: CUDA int32 tensor of one element, receives RLE8_SH_DONE / RLE8_SH_CAPACITY."""
+    for t, what in ((src, "src"), (dst, "dst"), (ws, "ws")):
+        _check_u8_cuda(t, what)
+    rc = _lib().hsrle_rle8_sh_compress_blocks_dev_async(ctypes.c_void_p(src.data_ptr()), src.numel(), block_size, ctypes.c_void_p(dst.data_ptr()), dst.numel(),
+                                                        ctypes.c_void_p(out_size.data_ptr()), ctypes.c_void_p(status.data_ptr()),
+                                                        ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(stream))
+    if rc != OK:
+        raise HsrleError(rc, "hsrle_rle8_sh_compress_blocks_dev_async")
+
+
+def rle8_sh_blocks_decompress_dev(container, info, dst, status, ws, first_block=0, block_count=None, stream=None):
+    """hsrle_rle8_sh_decompress_blocks_dev_async: enqueue the decompression of blocks [first_block, first_block + block_count) of the container in
+    the CUDA uint8 tensor `container` into `dst` (>= info.uncompressedSize bytes; block i lands at i * blockSize).  status: CUDA int32 tensor of one
+    element, receives RLE8_SH_DONE / RLE8_SH_MALFORMED."""
+    for t, what in ((container, "container"), (dst, "dst"), (ws, "ws")):
+        _check_u8_cuda(t, what)
+    count = info.blockCount - first_block if block_count is None else block_count
+    rc = _lib().hsrle_rle8_sh_decompress_blocks_dev_async(ctypes.c_void_p(container.data_ptr()), ctypes.byref(info), first_block, count,
+                                                          ctypes.c_void_p(dst.data_ptr()), dst.numel(), ctypes.c_void_p(status.data_ptr()),
+                                                          ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(stream))
+    if rc != OK:
+        raise HsrleError(rc, "hsrle_rle8_sh_decompress_blocks_dev_async")
+
+
+def rle8_sh_blocks_compress_host(data, block_size=0, out_cap=None):
+    """hsrle_rle8_sh_compress_blocks_host: (status, container bytes) of host bytes.  out_cap defaults to rle8_sh_blocks_bound."""
+    data = bytes(data)
+    cap = rle8_sh_blocks_bound(len(data), block_size) if out_cap is None else out_cap
+    out = ctypes.create_string_buffer(max(cap, 1))
+    total = ctypes.c_uint64(0)
+    rc = _lib().hsrle_rle8_sh_compress_blocks_host(data, len(data), block_size, out, cap, ctypes.byref(total))
+    return rc, out.raw[: total.value] if rc == OK else b""
+
+
+def rle8_sh_blocks_decompress_host(container, out_cap):
+    """hsrle_rle8_sh_decompress_blocks_host: (status, uncompressed bytes) of a container in host bytes."""
+    container = bytes(container)
+    out = ctypes.create_string_buffer(max(out_cap, 1))
+    size = ctypes.c_uint64(0)
+    rc = _lib().hsrle_rle8_sh_decompress_blocks_host(container, len(container), out, out_cap, ctypes.byref(size))
+    return rc, out.raw[: size.value] if rc == OK else b""

@@ -759,6 +759,71 @@ int hsrle_rle8_sh_decompress_dev_async(const void *dStream, uint64_t streamSize,
                                        void *stream);
 void hsrle_rle8_sh_tuning(uint32_t stretchSymbols, uint32_t walkWindow, uint32_t serialState);
 
+/*
+ * The rle8_sh BLOCK CONTAINER: many independent rle8_sh streams per call -- the throughput path of the codec.  The input is cut into blocks of
+ * blockSize bytes and block stream i is EXACTLY what rle8_sh_compress returns for input bytes [i B, min((i + 1) B, n)), its own 8-byte header
+ * included; with thousands of blocks in flight the passes that are one wave or one lane inside a stream stop being serial on the device, and a
+ * caller can shard the container and decode it by block range.  All fields little endian:
+ *   [ 0] char     magic[8] = "HSRLESHB"
+ *   [ 8] uint32_t version  = 1
+ *   [12] uint32_t reserved = 0
+ *   [16] uint64_t uncompressedSize
+ *   [24] uint32_t blockSize      (a multiple of 128, 128 .. 2^20; the last block may be shorter)
+ *   [28] uint32_t blockCount     = ceil(uncompressedSize / blockSize)
+ *   [32] uint64_t payloadSize
+ *   [40] uint64_t totalSize      = 64 + 8 * (blockCount + 1) + payloadSize + 32
+ *   [48] uint8_t  zero[16]
+ *   [64] uint64_t offset[blockCount + 1]   relative to the payload start; offset[0] = 0, offset[blockCount] = payloadSize
+ *        payload: the block streams back to back, at any byte address
+ *        32 zero bytes
+ * It is not a section-2 container (HSRLE_CODEC_COUNT stays what it is): hsrle_container_info_host refuses this magic and the info functions here
+ * refuse "HSRLEKIT".  blockSize 0 means 4096 everywhere.
+ * bound: header + table + the sum of hsrle_rle8_sh_capacity(bytes of block i) + 32: always suffices.  0 for a bad block size, inSize == 0 or a block
+ *   count that does not fit 32 bits.
+ * workspace_size: a function of min(blocks, blocks in flight) and blockSize, NOT of inSize: blocks go through the passes in groups, each block of a
+ *   group in a slot that is the workspace of a single stream of blockSize bytes (about 11 bytes per input byte to encode, 24 per output byte to
+ *   decode).  A decode of a block range needs the size for (blocks of the range) * blockSize bytes.  0 where bound is 0.
+ * info_host / info_dev: HSRLE_ERR_ARGUMENT for a null pointer or fewer than 64 bytes, HSRLE_ERR_FORMAT for a header that breaks any line above or
+ *   a totalSize above containerSize.  info_dev reads the header from the device and synchronises the stream, like hsrle_container_info_dev.
+ * The two _dev_async calls are ENQUEUE-ONLY like the single-stream calls above: nothing allocates, synchronises or reads device memory, a HIP graph
+ *   can capture them; what has to be zero is zeroed by a kernel, every word a kernel reads was written by a kernel before, workspace contents do
+ *   not matter.  Buffers at any byte address, not overlapping; dOutSize: a device word, 8-byte aligned; dStatus: a device word, 4-byte aligned.
+ *   Refused on the host before anything is enqueued: a null pointer, a bad block size, inSize == 0, overlapping buffers, misaligned words, an info
+ *   whose fields contradict each other, a block range outside the container or of no blocks (HSRLE_ERR_ARGUMENT); a workspace too small, an
+ *   outCapacity under header + table + pad (compress) or under uncompressedSize (decompress) (HSRLE_ERR_CAPACITY).
+ * compress: *dOutSize receives totalSize and *dStatus HSRLE_RLE8_SH_DONE; the container is complete, header included, and nothing is written at or
+ *   beyond totalSize.  If the container does not fit outCapacity: HSRLE_RLE8_SH_CAPACITY, *dOutSize 0, the first 8 bytes of dOut are not the magic,
+ *   nothing is written at or beyond outCapacity and what lies inside it is unspecified (the groups in front of the one that did not fit have
+ *   written their streams).  The block streams are written straight to their final address: there is no staging copy of the payload.
+ * decompress: decodes blocks [firstBlock, firstBlock + blockCount) into dOut + firstBlock * blockSize (the section-2 convention).  The offset table
+ *   is read on the device and trusted in nothing: an entry is bad when offset[i] > offset[i + 1] or offset[i + 1] > payloadSize.  A block is
+ *   MALFORMED when its entry is bad or its stream is, by every refusal rule of hsrle_rle8_sh_decompress_dev_async with the block's own
+ *   uncompressed size and its entry's length as the stream size; NONE of its output bytes is written, the other blocks are decoded, and *dStatus
+ *   receives HSRLE_RLE8_SH_MALFORMED if any block was, else HSRLE_RLE8_SH_DONE.  Never a byte outside the decoded range of dOut is written.
+ *   The symbol state of a block is followed by one lane (the serial pass of the single-stream decoder; a block has few records); stretchSymbols
+ *   and walkWindow of hsrle_rle8_sh_tuning are honoured, serialState has nothing to choose here.
+ * The _host calls stage host buffers per device like the functions above: HSRLE_OK / HSRLE_ERR_*; a malformed block is HSRLE_ERR_FORMAT.
+ * hsrle_rle8_sh_blocks_tuning: blocks in flight (0 = the default: 32 MiB of input per group, at least 256 and at most 8192 blocks -- DESIGN.md 4.9).
+ *   Any value gives the same bytes.  PROCESS-GLOBAL, for tests.
+ */
+typedef struct hsrle_rle8_sh_blocks_info
+{
+  uint64_t uncompressedSize;
+  uint32_t blockSize, blockCount;
+  uint64_t payloadSize, totalSize;
+} hsrle_rle8_sh_blocks_info_t;
+uint64_t hsrle_rle8_sh_blocks_bound(uint64_t inSize, uint32_t blockSize);
+uint64_t hsrle_rle8_sh_blocks_workspace_size(int decode, uint64_t inSize, uint32_t blockSize);
+int hsrle_rle8_sh_blocks_info_host(const void *pContainer, uint64_t containerSize, hsrle_rle8_sh_blocks_info_t *pInfo);
+int hsrle_rle8_sh_blocks_info_dev(const void *dContainer, uint64_t containerSize, hsrle_rle8_sh_blocks_info_t *pInfo, void *stream);
+int hsrle_rle8_sh_compress_blocks_dev_async(const void *dIn, uint64_t inSize, uint32_t blockSize, void *dOut, uint64_t outCapacity, uint64_t *dOutSize, uint32_t *dStatus,
+                                            void *dWorkspace, uint64_t workspaceSize, void *stream);
+int hsrle_rle8_sh_decompress_blocks_dev_async(const void *dContainer, const hsrle_rle8_sh_blocks_info_t *info, uint32_t firstBlock, uint32_t blockCount, void *dOut,
+                                              uint64_t outCapacity, uint32_t *dStatus, void *dWorkspace, uint64_t workspaceSize, void *stream);
+int hsrle_rle8_sh_compress_blocks_host(const void *pIn, uint64_t inSize, uint32_t blockSize, void *pOut, uint64_t outCapacity, uint64_t *pContainerSize);
+int hsrle_rle8_sh_decompress_blocks_host(const void *pContainer, uint64_t containerSize, void *pOut, uint64_t outCapacity, uint64_t *pUncompressedSize);
+void hsrle_rle8_sh_blocks_tuning(uint32_t blocksInFlight);
+
 int hsrle_kernel_waves_per_cu(int codec, int decode);
 const char *hsrle_version(void);
 
