@@ -149,7 +149,7 @@ int hsrle_low_entropy_decompress_dev(const void *dStream, uint64_t streamSize, v
   const uint32_t dataStart = 8u + 33u + listed;
   if ((uint64_t)expIn > streamSize || dataStart > expIn || expOut == 0u || expIn > 0xFFFFFF00u) return HSRLE_ERR_FORMAT;   // (the last: the piece arithmetic of le_decode_async is 32 bit, as on the host path)
   if (outCapacity < expOut) return HSRLE_ERR_CAPACITY;
-  // (the first 256 bytes of the workspace: the status words)
+  // (the first 256 bytes of the workspace: the status words; word 2 = the attempts, include/hsrle.h)
   const int rc = le_decode_attempts(dStream, expIn, dataStart, expOut, dOut, outCapacity, (uint8_t *)dWorkspace + 256, workspaceSize - 256, (uint32_t *)dWorkspace, st);
   if (rc == HSRLE_OK && pUncompressedSize) *pUncompressedSize = expOut;
   return rc;

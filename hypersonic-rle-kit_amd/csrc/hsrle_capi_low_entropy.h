@@ -188,8 +188,8 @@ static int le_encode_async(const void *dIn, uint32_t n, void *dOut, uint64_t out
   return le_encode_pieces((const uint8_t *)dIn, n, t, runStart4, maxLen, (uint8_t *)dOut, outCapacity, ws, p, dStatus, st);
 }
 
-// dStream: the stream (nothing at or beyond streamSize is read), dataStart = 8 + 33 + listed symbols (the caller has read the header).  dStatus: two
-// words ([0] error bits, [1] "a piece's parity could not be found within kLeCarryLimit bytes").  onePiece: decode with ONE wave (the fallback).
+// dStream: the stream (nothing at or beyond streamSize is read), dataStart = 8 + 33 + listed symbols (the caller has read the header).  dStatus: three
+// words ([0] error bits, [1] "a piece's parity could not be found within kLeCarryLimit bytes", [2] 1, or 2 with onePiece).  onePiece: decode with ONE wave (the fallback).
 static int le_decode_async(const void *dStream, uint32_t streamSize, uint32_t dataStart, uint32_t expOut, void *dOut, uint64_t outCapacity, void *dWs, uint64_t wsSize, uint32_t *dStatus,
                            bool onePiece, hipStream_t st)
 {
@@ -205,7 +205,7 @@ static int le_decode_async(const void *dStream, uint32_t streamSize, uint32_t da
   uint64_t *outStart = (uint64_t *)(ws + p.offOffsets);
   if (zero_async(dStatus, 8, st) != hipSuccess)
     return HSRLE_ERR_DEVICE;
-  hipLaunchKernelGGL(k_le_carry, dim3((p.pieces + 63u) / 64u), dim3(64), 0, st, (const uint8_t *)dStream, (uint64_t)streamSize, G, p.pieces, carry, dStatus);
+  hipLaunchKernelGGL(k_le_carry, dim3((p.pieces + 63u) / 64u), dim3(64), 0, st, (const uint8_t *)dStream, (uint64_t)streamSize, G, p.pieces, carry, dStatus, onePiece ? 2u : 1u);
   hipLaunchKernelGGL(k_le_decode_wave<true>, dim3(p.pieces), dim3(64), 0, st, (const uint8_t *)dStream, (uint64_t)streamSize, (uint8_t *)dOut, dStatus, expOut, G, p.pieces,
                      (const uint32_t *)carry, (const uint64_t *)nullptr, sizes);
   if (scan_sizes(sizes, p.pieces, outStart, ws, p.levels, st) != hipSuccess)

@@ -44,6 +44,10 @@ __device__ __forceinline__ uint32_t rle8m_tables(const uint8_t *__restrict__ s, 
     if (lane < 8u) rleBits[lane] = ld32(s + info + 4u * lane);
     for (uint32_t k = lane; k < 256u; k += 64u) listed[k] = 0;
     __syncthreads();
+    // A symbol may be listed twice, and then the LAST listing counts (include/hsrle.h; the reference, rle8_low_entropy_cpu.c:579-584).  Steps come in
+    // program order; within a step the lanes that name one symbol store to one LDS byte in one instruction, and this relies on the highest lane's store
+    // being the one that stays, as it does on gfx950.  Nothing in the language promises that: tests/test_gpu_low_entropy_grammar.py (form.list.dup,
+    // form.list.dup_short) holds it, and a build for other hardware that fails there needs a max over k here (and in le_tables below).
     for (uint32_t k = lane; k < listedCount; k += 64u)
     {
       const uint32_t sym = s[info + 33u + k];
@@ -984,6 +988,7 @@ __device__ __forceinline__ uint32_t le_tables(const uint8_t *__restrict__ s, uin
     if (lane < 8u) rleBits[lane] = ld32(s + info + 4u * lane);
     for (uint32_t k = lane; k < 256u; k += 64u) listed[k] = 0;
     __syncthreads();
+    // (two listings of one symbol: the last one counts, by the order of the stores -- see rle8m_tables)
     for (uint32_t k = lane; k < listedCount; k += 64u)
     {
       const uint32_t sym = s[info + 33u + k];
@@ -1012,10 +1017,13 @@ __device__ __forceinline__ uint32_t le_tables(const uint8_t *__restrict__ s, uin
 // carry[k]: parity of the stretch of flagged-valued bytes right in front of piece k (piece k starts at dataStart + k G): the piece's
 // first byte is a repeat code iff it is odd.  One lane per piece, a backward scan that ends at the first byte whose value is not flagged
 // (typically within a few bytes); a stretch of kLeCarryLimit bytes sets RLE8M_ERR_HEADER in status[1] and the caller decodes with one wave.
-__global__ __launch_bounds__(64) void k_le_carry(const uint8_t *__restrict__ s, uint64_t streamBytes, uint32_t G, uint32_t Q, uint32_t *__restrict__ carry, uint32_t *__restrict__ status)
+// status[2] = attempt: which attempt of le_decode_attempts this is (1: many waves, 2: the one wave), for whoever looks at the words afterwards.
+__global__ __launch_bounds__(64) void k_le_carry(const uint8_t *__restrict__ s, uint64_t streamBytes, uint32_t G, uint32_t Q, uint32_t *__restrict__ carry, uint32_t *__restrict__ status,
+                                                 uint32_t attempt)
 {
   __shared__ uint32_t rleBits[8];
   const uint32_t lane = threadIdx.x;
+  if (blockIdx.x == 0u && lane == 0u && status) status[2] = attempt;
   const uint32_t expIn = ld32(s);
   if (lane < 8u) rleBits[lane] = ld32(s + 8u + 4u * lane);
   __syncthreads();

@@ -806,6 +806,32 @@ def rle8m_bounds(sections, in_size):
     return int(L.rle8m_compress_bounds(ctypes.c_uint32(sections), ctypes.c_uint32(in_size)))
 
 
+def low_entropy_decompress_workspace_size(stream_size):
+    """hsrle_low_entropy_decompress_workspace_size: bytes of device workspace for the decode of an unsectioned stream of `stream_size` bytes."""
+    L = _lib()
+    L.hsrle_low_entropy_decompress_workspace_size.restype = ctypes.c_uint64
+    return int(L.hsrle_low_entropy_decompress_workspace_size(ctypes.c_uint64(stream_size)))
+
+
+def low_entropy_decompress_dev(stream_tensor, dst, workspace, stream=None):
+    """hsrle_low_entropy_decompress_dev: decode the device-resident unsectioned low-entropy stream into `dst` (uint8 CUDA tensors; synchronises).
+    Returns (status code, uncompressed size): OK, ERR_FORMAT for a stream that is refused, ... -- the code is returned, not raised."""
+    for t, what in ((stream_tensor, "stream"), (dst, "dst"), (workspace, "workspace")):
+        _check_u8_cuda(t, what)
+    L = _lib()
+    L.hsrle_low_entropy_decompress_dev.restype = ctypes.c_int
+    L.hsrle_low_entropy_decompress_dev.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+    size = ctypes.c_uint32(0)
+    rc = L.hsrle_low_entropy_decompress_dev(ctypes.c_void_p(stream_tensor.data_ptr()), stream_tensor.numel(), ctypes.c_void_p(dst.data_ptr()), dst.numel(),
+                                            ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), ctypes.byref(size), _stream_ptr(stream))
+    return int(rc), int(size.value)
+
+
+def low_entropy_decode_attempts(workspace):
+    """Decode attempts of the last low_entropy_decompress_dev on the workspace tensor: 1, or 2 where the one-wave fallback ran (include/hsrle.h)."""
+    return int(workspace[8:12].cpu().numpy().view("<u4")[0])
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # the multi-move-to-front transforms (include/hsrle.h section 5; reference: src/rle.h:420-438)
 

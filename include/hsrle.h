@@ -586,7 +586,16 @@ uint32_t rle8_low_entropy_short_compress_with_info(const uint8_t *pIn, const uin
 uint32_t rle8_low_entropy_short_decompress_with_info(const uint8_t *pIn, const uint8_t *pEnd, const rle8_low_entropy_decompress_info_t *pDecompressInfo, uint8_t *pOut, const uint32_t expectedOutSize);
 
 /* The same, device resident (variant: bit 0 the Short form, bit 1 only_max_frequency).  Compress only enqueues (the stream's size is its
- * first u32; *dStatus != 0: the stream did not fit `outCapacity`); decompress reads the header and the verdict (two stream synchronisations). */
+ * first u32; *dStatus != 0: the stream did not fit `outCapacity`); decompress reads the header and the verdict (two stream synchronisations).
+ * A stream that is refused (HSRLE_ERR_FORMAT) leaves nothing written outside dOut[0 .. outCapacity); what dOut itself holds then is not defined.
+ *   For tests and measurements: behind a decompress call that got as far as decoding, word 2 of the workspace (bytes 8 .. 11) is the number of
+ *   decode attempts: 1 = many waves on the one stream; 2 = a piece of the stream had 65 536 or more flagged-valued bytes right in front of it, the
+ *   backward scan for its symbol / code parity gave up, and ONE wave decoded the whole stream once more (same bytes, much slower).
+ * Every decoder of this codec here -- these, the drop-in names above and the rle8m ones -- reads the header as its grammar says: of two listings of
+ * one symbol the last one counts (as in the reference, rle8_low_entropy_cpu.c:579-584), and a stream in which all 256 symbols carry repeat codes
+ * decodes like any other.  The reference counts the flagged symbols in a uint8_t (rle8_low_entropy_cpu.c:940-945): 256 wrap to 0, it then copies
+ * the stream as if nothing were flagged and does not give back what its own encoders wrote (2 304 bytes -- the 256 values in runs of 3, three times over --
+ * are such an input).  That is not reproduced. */
 uint64_t hsrle_low_entropy_workspace_size(uint32_t inSize);
 int hsrle_low_entropy_compress_dev_async(const void *dIn, uint32_t inSize, int variant, void *dOut, uint64_t outCapacity, void *dWorkspace, uint64_t workspaceSize, uint32_t *dStatus, void *stream);
 uint64_t hsrle_low_entropy_decompress_workspace_size(uint64_t streamSize);
