@@ -74,13 +74,17 @@ static hipError_t launch_le_stats(const uint8_t *dIn, uint32_t n, Rle8mTables *t
 
 static uint32_t rle8m_bounds(uint32_t sections, uint32_t n) { return n + (256 / 8) + 1 + 256 + 4u * (2u + sections - 1u + 1u); }
 
+// The encoders keep words in their workspace -- counters that take atomics, 64-bit offsets -- at multiples of 256 bytes from its start, and zero the status
+// word with a word store: a workspace or a status word at an odd address is refused on the host (input and output may start at any byte).
+static inline bool encode_words_aligned(const void *dWs, const uint32_t *dStatus) { return ((uintptr_t)dWs & 15u) == 0u && ((uintptr_t)dStatus & 3u) == 0u; }
+
 // the caller has checked device_ok()
 // maxLen / onlyMax: the four unsectioned encoders share these kernels (rle8_low_entropy[_short]_compress[_only_max_frequency]: runs are cut
 // every 255 or 32 bytes, and either every symbol whose runs average >= 2 carries repeat codes or only the one that saves the most)
 static int rle8m_encode_async(const void *dIn, uint32_t n, uint32_t sections, void *dOut, uint64_t outCapacity, void *dWs, uint64_t wsSize, uint32_t *dStatus, hipStream_t st,
                               uint32_t maxLen = 255u, uint32_t onlyMax = 0u)
 {
-  if (!dIn || !dOut || !dWs || n == 0 || sections == 0)
+  if (!dIn || !dOut || !dWs || n == 0 || sections == 0 || !encode_words_aligned(dWs, dStatus))
     return HSRLE_ERR_ARGUMENT;
   if (outCapacity < rle8m_bounds(sections, n))
     return HSRLE_ERR_CAPACITY;
@@ -169,7 +173,7 @@ static int le_encode_pieces(const uint8_t *dIn, uint32_t n, const Rle8mTables *t
 // caller's buffer there, rle8_low_entropy_cpu.c:476).  Only enqueues.  The stream's size is its first u32.
 static int le_encode_async(const void *dIn, uint32_t n, void *dOut, uint64_t outCapacity, void *dWs, uint64_t wsSize, uint32_t *dStatus, uint32_t maxLen, uint32_t onlyMax, hipStream_t st)
 {
-  if (!dIn || !dOut || !dWs || n == 0)
+  if (!dIn || !dOut || !dWs || n == 0 || !encode_words_aligned(dWs, dStatus))
     return HSRLE_ERR_ARGUMENT;
   if (outCapacity < le_bounds(n))
     return HSRLE_ERR_CAPACITY;
@@ -178,7 +182,7 @@ static int le_encode_async(const void *dIn, uint32_t n, void *dOut, uint64_t out
     return HSRLE_ERR_CAPACITY;
   uint8_t *ws = (uint8_t *)dWs;
   Rle8mTables *t = (Rle8mTables *)(ws + p.offTables);
-  if (zero_async(t, sizeof(Rle8mTables), st) != hipSuccess || (dStatus && zero_async(dStatus, 8, st) != hipSuccess))
+  if (zero_async(t, sizeof(Rle8mTables), st) != hipSuccess || (dStatus && zero_async(dStatus, 4, st) != hipSuccess))   // (ONE word: include/hsrle.h)
     return HSRLE_ERR_DEVICE;
   const uint32_t *runStart4 = nullptr;
   if (launch_le_stats((const uint8_t *)dIn, n, t, maxLen, ws + p.offStats, st, 32768u, &runStart4) != hipSuccess)

@@ -806,6 +806,41 @@ def rle8m_bounds(sections, in_size):
     return int(L.rle8m_compress_bounds(ctypes.c_uint32(sections), ctypes.c_uint32(in_size)))
 
 
+def low_entropy_bounds(in_size):
+    L = _lib()
+    L.rle8_low_entropy_compress_bounds.restype = ctypes.c_uint32
+    return int(L.rle8_low_entropy_compress_bounds(ctypes.c_uint32(in_size)))
+
+
+def low_entropy_workspace_size(n):
+    """hsrle_low_entropy_workspace_size: bytes of device workspace for the encode of `n` input bytes (0 for n == 0)."""
+    L = _lib()
+    L.hsrle_low_entropy_workspace_size.restype = ctypes.c_uint64
+    return int(L.hsrle_low_entropy_workspace_size(ctypes.c_uint32(n)))
+
+
+def low_entropy_compress_dev(src, variant, dst, workspace, status, stream=None):
+    """hsrle_low_entropy_compress_dev_async: enqueue the unsectioned low-entropy encode of the uint8 CUDA tensor `src` into `dst` (capacity >=
+    low_entropy_bounds) -- variant: bit 0 the Short form, bit 1 only_max_frequency; `status`: an int32 CUDA tensor, one word.  Nothing is read back: the
+    stream's size is its first u32.  Returns the status code (OK, ERR_CAPACITY, ERR_ARGUMENT, ...): returned, not raised."""
+    for t, what in ((src, "src"), (dst, "dst"), (workspace, "workspace")):
+        _check_u8_cuda(t, what)
+    L = _lib()
+    L.hsrle_low_entropy_compress_dev_async.restype = ctypes.c_int
+    L.hsrle_low_entropy_compress_dev_async.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                                       ctypes.c_void_p, ctypes.c_void_p]
+    sp = ctypes.c_void_p(status.data_ptr()) if status is not None else None
+    return int(L.hsrle_low_entropy_compress_dev_async(ctypes.c_void_p(src.data_ptr()), src.numel(), variant, ctypes.c_void_p(dst.data_ptr()), dst.numel(),
+                                                      ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), sp, _stream_ptr(stream)))
+
+
+def encode_stats_words(workspace):
+    """(prob, pcount), 256 uint32 each: the run statistics a finished low_entropy_compress_dev / rle8m_compress_async left in the first 2 048 bytes of its
+    workspace tensor (include/hsrle.h: for tests and measurements)."""
+    words = workspace[:2048].cpu().numpy().view("<u4")
+    return words[:256].copy(), words[256:].copy()
+
+
 def low_entropy_decompress_workspace_size(stream_size):
     """hsrle_low_entropy_decompress_workspace_size: bytes of device workspace for the decode of an unsectioned stream of `stream_size` bytes."""
     L = _lib()

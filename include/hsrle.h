@@ -595,7 +595,13 @@ uint32_t rle8_low_entropy_short_decompress_with_info(const uint8_t *pIn, const u
  * one symbol the last one counts (as in the reference, rle8_low_entropy_cpu.c:579-584), and a stream in which all 256 symbols carry repeat codes
  * decodes like any other.  The reference counts the flagged symbols in a uint8_t (rle8_low_entropy_cpu.c:940-945): 256 wrap to 0, it then copies
  * the stream as if nothing were flagged and does not give back what its own encoders wrote (2 304 bytes -- the 256 values in runs of 3, three times over --
- * are such an input).  That is not reproduced. */
+ * are such an input).  That is not reproduced.
+ * The two encoders (hsrle_low_entropy_compress_dev_async, hsrle_rle8m_compress_dev_async): dIn and dOut at any byte address; dWorkspace 16-byte aligned, its
+ * contents do not matter; dStatus ONE device word, 4-byte aligned (or NULL) -- a misaligned workspace or status word is HSRLE_ERR_ARGUMENT.  HSRLE_ERR_ARGUMENT and
+ * HSRLE_ERR_CAPACITY mean that nothing was enqueued and nothing written.  What a call leaves in dOut behind the stream's end is not defined.
+ *   For tests and measurements: behind either compress call the first 2 048 bytes of the workspace are the run statistics the tables were made from --
+ *   prob[256], then pcount[256], uint32 each (a maximal run of L bytes adds L to prob and L / 255 + 1 to pcount -- L / 32 + 1 for the Short form -- and the
+ *   run that ends the input adds 1 to pcount whatever its length, rle8_low_entropy_cpu.c:264-296). */
 uint64_t hsrle_low_entropy_workspace_size(uint32_t inSize);
 int hsrle_low_entropy_compress_dev_async(const void *dIn, uint32_t inSize, int variant, void *dOut, uint64_t outCapacity, void *dWorkspace, uint64_t workspaceSize, uint32_t *dStatus, void *stream);
 uint64_t hsrle_low_entropy_decompress_workspace_size(uint64_t streamSize);
