@@ -556,7 +556,7 @@ __device__ __forceinline__ void ppL_block(uint64_t U, uint32_t B, uint32_t b, ui
         }
         else
         {
-        const uint32_t c7 = cfield <= MAXC ? cfield : 1u, r7 = rng <= MAXR ? rng : 1u;   // (1: a 16 bit field follows; nothing in a block needs 32)
+        const uint32_t c7 = cfield <= MAXC ? cfield : 1u, r7 = rng <= MAXR ? rng : 1u;   // (1: a 16 bit field follows; nothing in a block needs 32 -- hsrle_codecs.h: kPpwListMaxBlock)
         pp_or_bytes(sh.img, a, (uint64_t)((mtf << MSH) | (c7 << RB) | r7), 2u); a += 2u;
         if (mtf == KU) { pp_or_bytes(sh.img, a, sym, SU); a += SU; }
         if (cBytes) { pp_or_bytes(sh.img, a, (uint64_t)cfield, 2u); a += 2u; }

@@ -8,7 +8,8 @@
 // boundary.  Pass 1 (one wave per block, window after window) keeps the list in LDS; the state record of a window holds it for pass 2 (one wave per window), which needs it
 // only where a window stored more runs than its records hold and repeats the decisions.  Everything else -- the match bits' history, runs that begin in front of the
 // window, the literal bytes in front of it -- is hsrle_encodeSpw.hip.h's.  The LUT / Short header forms choose their field widths by value (16 or 32 bits beyond the packed
-// field); the host keeps these codecs to blocks below 1 MiB, where the reference's penalty thresholds (0xFFFFF: rleX_Xsl.h:130, rleX_Xsl_short.h:178) cannot be reached.
+// field); the host keeps these codecs to blocks of at most kPpwListMaxBlock, where the reference's penalty thresholds (0xFFFFF: rleX_Xsl.h:130, rleX_Xsl_short.h:197) cannot be
+// reached (hsrle_codecs.h asserts it beside the constant).
 #pragma once
 
 #include "hsrle_encodeLp.hip.h"

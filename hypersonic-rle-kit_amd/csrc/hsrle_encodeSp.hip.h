@@ -301,7 +301,7 @@ __device__ __forceinline__ void ppS_block(const uint8_t *__restrict__ in, uint64
           const uint32_t scu = AL ? count / SU - TR::SMINS / SU + 2u : count - TR::SMINS + 2u;
           const bool pack1 = gp <= TR::SMAXPR && scu - 2u <= TR::SMAXPC;
           uint32_t pen = (SH1 && !sm) ? SU : 0u;
-          if (!pack1) pen += 2u + (range <= TR::SMAXTR ? 0u : 2u) + (scu <= TR::SMAXTC ? 0u : 2u);      // (nothing in a block needs a 32 bit field)
+          if (!pack1) pen += 2u + (range <= TR::SMAXTR ? 0u : 2u) + (scu <= TR::SMAXTC ? 0u : 2u);      // (nothing in a block needs a 32 bit field, nor the 20 bit penalty term: hsrle_codecs.h asserts the bound beside kPpwListMaxBlock)
           if (!SH3 && !(count >= TR::SMINL || count >= TR::SMINS + pen)) return 0;
           return pack1 ? 1 : 2;
         }
@@ -393,7 +393,7 @@ __device__ __forceinline__ void ppS_block(const uint8_t *__restrict__ in, uint64
         uint32_t a = at0;
         if constexpr (LUT)
         {
-          const uint32_t c7 = cfield <= 127u ? cfield : 1u, r7 = rng <= 127u ? rng : 1u;   // (1: a 16 bit field follows; nothing in a block needs 32)
+          const uint32_t c7 = cfield <= 127u ? cfield : 1u, r7 = rng <= 127u ? rng : 1u;   // (1: a 16 bit field follows; nothing in a block needs 32 -- hsrle_codecs.h: kPpwListMaxBlock)
           pp_or_bytes(sh.img, a, (uint64_t)((mtf << 14) | (c7 << 7) | r7), 2u); a += 2u;
           if (mtf == 3u) { pp_or_bytes(sh.img, a, sym, SU); a += SU; }
           if (cBytes) { pp_or_bytes(sh.img, a, (uint64_t)cfield, 2u); a += 2u; }

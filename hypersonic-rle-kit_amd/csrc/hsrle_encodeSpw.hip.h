@@ -326,7 +326,8 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
           const uint32_t scu = AL ? count / SU - TR::SMINS / SU + 2u : count - TR::SMINS + 2u;
           const bool pack1 = gp <= TR::SMAXPR && scu - 2u <= TR::SMAXPC;
           uint32_t pen = (SH1 && !sm) ? SU : 0u;
-          if (!pack1) pen += 2u + (range <= TR::SMAXTR ? 0u : 2u) + (scu <= TR::SMAXTC ? 0u : 2u);
+          // (rleX_Xsl_short.h:197: above 20 bits a field costs 4 -- a chunk of a monolithic stream has no length limit; blocks end below it, hsrle_codecs.h: kPpwListMaxBlock)
+          if (!pack1) pen += 2u + (range <= 0xFFFFFu ? (range <= TR::SMAXTR ? 0u : 2u) : 4u) + (scu <= 0xFFFFFu ? (scu <= TR::SMAXTC ? 0u : 2u) : 4u);
           if (!SH3 && !(count >= TR::SMINL || count >= TR::SMINS + pen)) return 0;
           return pack1 ? 1 : 2;
         }
@@ -390,7 +391,8 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
     const uint32_t cfield = LUT ? (AL ? count / SU - 3u / SU + 2u : count - 1u) : (AL ? count / SU - SHORT / SU + 1u : count - SHORT + 1u);
     const uint32_t cMax = (PK || LUT) ? 127u : 255u;
     // (blocks above 64 KiB: counts and ranges beyond 16 bits exist -- the LUT / Short forms then say 0 in the packed field and a 32 bit field follows: rleX_Xsl.h:190-250,
-    //  rleX_Xsl_short.h:216-357; the host keeps these codecs to blocks below 1 MiB, where the reference's penalty thresholds (0xFFFFF) cannot be reached)
+    //  rleX_Xsl_short.h:216-357.  The reference's penalty steps again at 0xFFFFF: block mode cannot get there -- the host keeps these codecs to blocks of at most
+    //  kPpwListMaxBlock, hsrle_codecs.h asserts it -- but a chunk of a monolithic stream can, and the Short `decide` above has the term)
     const uint32_t cBytes = LUT ? (cfield <= 127u ? 0u : (cfield <= 0xFFFFu ? 2u : 4u)) : (cfield <= cMax ? 1u : 5u);
     const uint32_t sBytes = MTF3 ? (mtf == 3u ? SU : 0u) : (((PK || SH1) && same) ? 0u : SU);
     const uint32_t rBytes = LUT ? (rng <= 127u ? 0u : (rng <= 0xFFFFu ? 2u : 4u)) : ((k == 1) ? 1u : (R7 ? 4u : 5u));
