@@ -775,7 +775,8 @@ __global__ __launch_bounds__(64) void k_encodeL_ppw_emit(PpwArgs a)
   const uint32_t recN = wave_lane(sv, 4 + 2 * K);
   PpLwCarry cs;
   cs.pos = wave_lane(sv, 0); cs.carL = wave_lane(sv, 1); cs.openStart = wave_lane(sv, 2); cs.carE = wave_lane(sv, 3);
-  cs.ended = false;
+  // (the window in front may have stored a run that reaches the block's end -- a block that ends 1 .. S - 1 bytes into a window: hsrle_encodeSpw.hip.h)
+  cs.ended = cs.carL >= n;
   wave_sync();
   ppLw_window<FAM, S, AL, 1>(d, n, w, cs, wave_lane(sv, 4 + 2 * K + 3), st, const_cast<uint32_t *>(myRecs), u, unitSize, a.payload + unitAt, sh, x, recN, rec0);
 }

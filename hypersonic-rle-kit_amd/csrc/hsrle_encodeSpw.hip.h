@@ -724,9 +724,10 @@ __global__ __launch_bounds__(64) void k_encodeS_ppw_emit(PpwArgs a)
   cs.lA = (uint64_t)wave_lane(sv, 6) | ((uint64_t)wave_lane(sv, 7) << 32);
   cs.lB = (uint64_t)wave_lane(sv, 8) | ((uint64_t)wave_lane(sv, 9) << 32);
   cs.lY = (uint64_t)wave_lane(sv, 10) | ((uint64_t)wave_lane(sv, 11) << 32);
-  // (chunks: a run stored in an earlier window may already reach the input's end -- its match stretch ends up to S bytes in front of that end, so in the
-  //  window in front of the last when the input ends 1 .. S - 1 bytes into a window: then lastRLE in front of the last window is the end)
-  cs.ended = MONO && cs.carL >= nT;
+  // (a run stored in an earlier window may already reach the input's end -- its match stretch ends up to S bytes in front of that end, so in the
+  //  window in front of the last when the input ends 1 .. S - 1 bytes into a window: then lastRLE in front of the last window is the end.  Blocks
+  //  as chunks: the scan pass carried `ended` over that edge and sized the unit for the short terminator)
+  cs.ended = cs.carL >= nT;
   wave_sync();
   ppSw_window<FAM, S, AL, 1, MONO>(d, n, nT, hasTerm, w, cs, wave_lane(sv, 15), nullptr, const_cast<uint32_t *>(myRecs), u, unitSize, a.payload + unitAt, sh, x, recN, rec0);
 }
