@@ -158,6 +158,26 @@ constexpr bool dec8_loop_lrh(Family fam, bool sgl)
 #endif
 }
 
+// Lazy run fill (hsrle_decode.hip.h, `S == 1`, uncapped rounds without an output window: the kernels with the full-row flush): the R section stores only the first
+// chunk of what it fills and marks the chunks that lie wholly inside the run behind it in a per-row bit mask; the full-row flush's serving lane reads the stored chunk
+// in front of a marked one instead and broadcasts its last byte.  Part of the rule like the section order above: the kernel asks with its family, SGL and ring, and every
+// kernel that was not measured keeps the stores.  Same-box A/B per row (profiles/r14_decode_run_fill.md, 2 GiB, run-distributed / video-shaped, against the spread
+// between two batches of the parent): the Packed multi kernel (the headline: -1.7 % time at 8 GiB; rle8_packed_multi +1.7 / +1.6 %), the plain multi kernel (rle8_multi
+// +1.0 / +2.5 %) and the 3-symbol list kernel (rle8_3symlut +1.8 / +1.2 %) gain on both shapes and take it.  The kernels of the Single ids lose on run data
+// (rle8_single -0.8 %, rle8_packed_single -0.7 % / +4.2 %, rle8_single_short -0.6 / -0.2 %), the Short kernels without and with a one-symbol list gain on run data only
+// (+3.2 / +0.1 %, +4.0 / 0.0 %), and the 7-symbol list kernel would lose a wave per SIMD (164 -> 170 VGPRs): they keep the stores.  So do the instantiations with the
+// 64-byte stream ring: those rows ran the 128-byte ring, nobody measured the small one, and the 64 mask bytes would be its eleventh LDS allocation granule of 1 280 bytes
+// (12 800 bytes are exactly ten: 12 waves per CU, which is also what the registers allow; eleven granules hold 11).
+// A/B builds: -DHSRLE_DEC8_LAZY=0 / 1 forces it on every 8 bit kernel that can take it, either ring.
+constexpr bool dec8_lazy_fill(Family fam, bool sgl, int ring)
+{
+#ifdef HSRLE_DEC8_LAZY
+  return HSRLE_DEC8_LAZY != 0;
+#else
+  return ring == 128 && (((fam == PACKED || fam == PLAIN) && !sgl) || fam == LUT3);
+#endif
+}
+
 struct DecodeVariant
 {
   Family fam;          // the kernel's FAM: Single ids decode with the multi kernels' general form, Greedy ids with the Short decoder of their grammar (the row's family)

@@ -625,6 +625,19 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
     fullOutAt[q] = fullRowOK ? ((uint32_t)q * RPI + lane / CPR) * B + (lane % CPR) * 16u : 0u;
   static_assert(RPI % 8 == 0, "the tile swizzle of row q * RPI + r must not depend on q");
 
+  // LAZY RUN FILL (dec8_lazy_fill(), hsrle_codecs.h: the decode rule).  The R section of the 8 bit loop stores the first chunk of what it fills -- merged with `acc`, as
+  // ever -- and nothing behind it: the chunks that lie WHOLLY inside the run behind that chunk get their bits set in the row's fillMask (bit k = chunk k of the tile
+  // row; a row begins with some section's first chunk, so bit 0 is never set), and the chunk the run ends in, if it ends inside one, lives in `acc` alone until the next
+  // section, or the block's tail, stores it.  Marked chunks are contiguous behind a stored chunk whose byte 15 is the run's symbol (the run covers >= 32 bytes from inside
+  // that chunk on), and no later section of the round writes below the write position.  The owner publishes the mask as a byte behind every pass (fillm[]: the slot order
+  // of publish(), so the eight rows a lane serves are one 8-byte read); the full-row flush's serving lane of (row, chunk c) reads chunk c' = the highest clear bit at or
+  // below c (c itself unless marked) and, where c' != c, broadcasts its byte 15.  Every other way out of a round -- the general flush: partial waves, block tails,
+  // lanes that stalled or ended in an error -- lets the owner write its marked chunks into the tile first (materialise, below), and then runs unchanged.
+  constexpr bool kLazy = S == 1 && T == 128 && Q == T && kFullRowFlush && dec8_lazy_fill((Family)FAM, SGL, R);
+  [[maybe_unused]] uint32_t fillMask = 0;
+  __shared__ __attribute__((aligned(8))) uint8_t fillm[64];
+  [[maybe_unused]] const uint32_t fillmAt = (lane % (uint32_t)RPI) * (uint32_t)CPR + lane / (uint32_t)RPI;
+
   [[maybe_unused]] bool skippedFlush = false;                          // capped rounds: the last trip went round again without a flush
   while (__ballot(!done && o < blen) != 0ull)
   {
@@ -901,8 +914,20 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
             const u32x4 v = u32x4{ sym4, sym4, sym4, sym4 };
             const u32x4 w = HS_MERGE_LOW(acc, v, c);
             lds_st128(row + (d0 ^ tsw), w);
-            for (uint32_t k = 16; k < total; k += 16)
-              lds_st128(row + (HS_ROWWRAP(d0 + k) ^ tsw), v);
+            if constexpr (kLazy)
+            {
+              // chunks d0 / 16 + 1 .. (d0 + total) / 16 - 1 are the run's symbol from end to end: marked, not stored (d0 + total <= T)
+              const uint32_t f = d0 >> 4, e = (d0 + total) >> 4;
+              fillMask |= ((1u << e) - 1u) & ~((2u << f) - 1u);
+            }
+            else
+            {
+#ifdef HSRLE_ABLATE_RUN_FILL  // timing-only diagnostic build: no chunk behind the first one of an R section is stored where the lazy fill could apply (output is wrong)
+              if constexpr (!(T == 128 && Q == T && kFullRowFlush))
+#endif
+              for (uint32_t k = 16; k < total; k += 16)
+                lds_st128(row + (HS_ROWWRAP(d0 + k) ^ tsw), v);
+            }
             acc = (total <= 16u) ? w : v;
             run -= m;
             o += m;
@@ -910,6 +935,7 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
         }
       }
 
+      if constexpr (kLazy) fillm[fillmAt] = (uint8_t)fillMask;          // (every pass: pass 1 may have added bits)
       done = (fl & F_DONE) != 0u;
       last = (fl & F_LAST) != 0u;
     }
@@ -1429,16 +1455,41 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
       if ((__builtin_amdgcn_ballot_w64(base == ubase) & __builtin_amdgcn_ballot_w64(o - fullRowT == ubase)) == ~0ull)
       {
         uint8_t *const waveOut = outw + ((uint64_t)wgFirst * B + ubase);
+        // lazy run fill: the masks of the eight rows this lane serves, row h + k in byte h + k
+        [[maybe_unused]] uint64_t rowMasks = 0ull;
+        if constexpr (kLazy) { rowMasks = lds_ld64(fillm + (lane / CPR) * (uint32_t)CPR); fillMask = 0u; }
 #pragma unroll
         for (int h = 0; h < CPR; h += FH)                                // (FH at a time: the general flush's order and register bound)
         {
           u32x4 fv[FH];
-#pragma unroll
-          for (int k = 0; k < FH; k++)
-            fv[k] = lds_ld128(tile + fullTileAt + (uint32_t)(h + k) * RPI * TS);
+          [[maybe_unused]] bool fromRun[FH];
 #pragma unroll
           for (int k = 0; k < FH; k++)
           {
+            if constexpr (kLazy)
+            {
+              // the stored chunk at or below this lane's: the highest clear mask bit among bits 0 .. c (bit 0 is always clear)
+              const uint32_t c = lane % CPR;
+              const uint32_t clear = ((2u << c) - 1u) & ~(uint32_t)(rowMasks >> (8 * (h + k)));
+              const uint32_t cs = 31u - (uint32_t)__builtin_clz(clear);
+              fromRun[k] = cs != c;
+              fv[k] = lds_ld128(tile + (lane / CPR) * (uint32_t)TS + (uint32_t)(h + k) * RPI * TS + ((cs << 4) ^ tsw_of(lane / CPR)));
+            }
+            else
+              fv[k] = lds_ld128(tile + fullTileAt + (uint32_t)(h + k) * RPI * TS);
+          }
+#pragma unroll
+          for (int k = 0; k < FH; k++)
+          {
+            if constexpr (kLazy)
+            {
+              // a marked chunk is 16 copies of byte 15 of the chunk read in its place (one selector for the four dwords, .w last)
+              const uint32_t sel = fromRun[k] ? 0x07070707u : 0x03020100u;
+              fv[k].x = __builtin_amdgcn_perm(fv[k].w, fv[k].x, sel);
+              fv[k].y = __builtin_amdgcn_perm(fv[k].w, fv[k].y, sel);
+              fv[k].z = __builtin_amdgcn_perm(fv[k].w, fv[k].z, sel);
+              fv[k].w = __builtin_amdgcn_perm(fv[k].w, fv[k].w, sel);
+            }
             // (no instruction: keeps the zero extension beside the store, which then takes the scalar pointer + 32-bit offset form.  Correct with any code
             //  generation, but the path's 40 instructions and the 8 VGPRs of the offsets are this compiler's: hoisted extensions come back as eight 64-bit
             //  pairs (166 VGPRs in the headline kernel).  Run tools/decode_resources.py --against the committed table after every toolchain change.)
@@ -1455,6 +1506,22 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
 
     // ---- flush: whole 16-byte chunks only.  A row that ends inside a chunk (lane starved, or the block tail) keeps that
     //      chunk in `acc` and re-writes it at tile offset 0 in the next round, so there is no byte-granular path ----
+    if constexpr (kLazy)
+    {
+      // lazy run fill, materialise: the owner writes its marked chunks, each 16 copies of the last byte of the chunk below it, walking upward (rare: a plain loop)
+      if (fillMask != 0u)
+      {
+#pragma unroll 1
+        for (uint32_t c = 1; c < (uint32_t)CPR; c++)
+          if (((fillMask >> c) & 1u) != 0u)
+          {
+            const uint32_t s = __builtin_amdgcn_perm(0u, lds_ld128(row + (((c - 1u) << 4) ^ tsw)).w, 0x03030303u);
+            lds_st128(row + ((c << 4) ^ tsw), u32x4{ s, s, s, s });
+          }
+        fillMask = 0u;
+      }
+      wave_sync();
+    }
     const uint32_t produced = o - base;
     const bool tailNow = active && o == blen && (produced & 15u) != 0u;   // only the last block of a buffer can have one
     // (capped rounds: whole 64-byte halves; everything at the block's end)
@@ -1526,6 +1593,7 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *__restrict_
     if (tailNow)
     {
       const uint32_t at = CAP != 0u ? (base & ((uint32_t)T - 1u)) : (chunks << 4);   // (capped rounds: base is already behind the flushed chunks)
+      if constexpr (kLazy) lds_st128(row + (at ^ tsw), acc);           // lazy run fill: a run that ends inside this chunk left it in `acc` alone
       for (uint32_t k = 0; k < (produced & 15u); k++)
       {
         const uint64_t P = (uint64_t)b * B + base + k;

@@ -9,7 +9,12 @@ Packets as the two synthetic generators of the benchmark give them (tests/hsrle_
   runs   literals 1 .. 63, run 2 .. 63, both uniform                                       (run-distributed(8): the headline)
   video  1 .. 9 literals, run 40 .. 159 with probability 1/4, else 10 .. 25                   (video-shaped)
 numpy only.  Prints, per generator and order: trips, H / L / R sections and literal / run chunk iterations per step.  tools/probe_kernel_stamps.py prints the
-same three section counts as the kernel's stamp build counts them."""
+same three section counts as the kernel's stamp build counts them.
+
+Lazy run fill (dec8_lazy_fill, hsrle_codecs.h): a second table counts the 16-byte LDS stores of the two copy sections.  Executed by the wave per step: literal chunk
+iterations + run chunk iterations as the loop stands; with the lazy fill an R section executes ONE store, so the interior run chunk iterations (run chunk iterations
+- R sections) go away.  Needed by a lane per step: its own literal and run chunks, and how many of its run chunks lie wholly inside the run behind the section's
+first chunk -- the chunks a lazy kernel marks for the flush instead of storing them."""
 import sys
 
 import numpy as np
@@ -32,7 +37,7 @@ def simulate(kind, order, waves=512, seed=1):
     lane = np.arange(n)
     nxt = np.zeros(n, dtype=np.int64)
     lit, run, o = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
-    count = dict(trips=0, H=0, L=0, R=0, lit_chunks=0, run_chunks=0)
+    count = dict(trips=0, H=0, L=0, R=0, lit_chunks=0, run_chunks=0, lane_lit=0.0, lane_run=0.0, lane_lazy=0.0)
     per_wave = lambda m: m.reshape(waves, LANES)
     steps = BLOCK // STEP
     for s in range(steps):
@@ -51,12 +56,15 @@ def simulate(kind, order, waves=512, seed=1):
                     need = act & (lit > 0) & (o < target)
                     m = np.minimum(lit, target - o) * need
                     count["lit_chunks"] += int(per_wave(((o & 15) + m + 15) // 16 * need).max(1).sum())
+                    count["lane_lit"] += float((((o & 15) + m + 15) // 16 * need).sum()) / LANES
                     o += m
                     lit -= m
                 else:
                     need = act & (lit == 0) & (run > 0) & (o < target)
                     m = np.minimum(run, target - o) * need
                     count["run_chunks"] += int(per_wave(((o & 15) + m + 15) // 16 * need).max(1).sum())
+                    count["lane_run"] += float((((o & 15) + m + 15) // 16 * need).sum()) / LANES
+                    count["lane_lazy"] += float((np.maximum(((o & 15) + m) // 16 - 1, 0) * need).sum()) / LANES      # chunks wholly inside the run, behind the first
                     o += m
                     run -= m
                 count[sec] += int(per_wave(need).any(1).sum())
@@ -77,10 +85,14 @@ def main(argv):
     orders = orders or ["HLR", "RHL", "LRH"]
     print("| data | order | trips per step | H sections | L | R | literal chunk iterations | run chunk iterations |")
     print("|---|---|---:|---:|---:|---:|---:|---:|")
-    for kind in ("runs", "video"):
-        for order in orders:
-            r = simulate(kind, order, waves, seed)
-            print("| %s | %s | %.2f | %.2f | %.2f | %.2f | %.1f | %.1f |" % (kind, " ".join(order), r["trips"], r["H"], r["L"], r["R"], r["lit_chunks"], r["run_chunks"]))
+    results = [(kind, order, simulate(kind, order, waves, seed)) for kind in ("runs", "video") for order in orders]
+    for kind, order, r in results:
+        print("| %s | %s | %.2f | %.2f | %.2f | %.2f | %.1f | %.1f |" % (kind, " ".join(order), r["trips"], r["H"], r["L"], r["R"], r["lit_chunks"], r["run_chunks"]))
+    print("\n| data | order | interior run chunk iterations | wide LDS stores executed per step | with the lazy fill | a lane needs: literal chunks | run chunks | of them marked, not stored |")
+    print("|---|---|---:|---:|---:|---:|---:|---:|")
+    for kind, order, r in results:
+        print("| %s | %s | %.1f | %.1f | %.1f | %.1f | %.1f | %.1f |" % (kind, " ".join(order), r["run_chunks"] - r["R"], r["lit_chunks"] + r["run_chunks"], r["lit_chunks"] + r["R"],
+                                                                      r["lane_lit"], r["lane_run"], r["lane_lazy"]))
 
 
 if __name__ == "__main__":
