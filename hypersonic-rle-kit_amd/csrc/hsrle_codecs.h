@@ -210,8 +210,10 @@ constexpr uint32_t kSplitPieces = 4u, kSplitPiecesMax = 8u;   // cut finder lane
 // (the plain / Packed codecs write 8 or 32 bit fields whatever the block size; the LUT / Short forms choose their field widths -- and the reference its penalties, with
 //  thresholds of 0xFFFFF: rleX_Xsl.h:130, rleX_Xsl_short.h:178 -- by the values: below 1 MiB per block no count or range gets there and "every run is stored" holds)
 constexpr uint32_t kPpwListMaxBlock = (1u << 20) - 128u;
-// The bound the block encoders of the list codecs rest on (hsrle_encodeSp / Lp / Lpw.hip.h and the block mode of hsrle_encodeSpw.hip.h leave the 20 bit term out): the largest
-// range of a block is its size + 2, the largest stored count below that.  The windowed encoders' CHUNK mode (chunk_mode() above) has no such bound and carries the term.
+// The bound the block encoders of the list codecs rest on: the largest range of a block is its size + 2, the largest stored count below that.  Who leaves the 20 bit
+// term out because of it: hsrle_encodeSp.hip.h (ppS_decide<.., WIDE = false>) and hsrle_encodeLp / Lpw.hip.h (stored_with).  hsrle_encodeSpw.hip.h instantiates
+// ppS_decide<.., WIDE = true> for all its kernels: its CHUNK mode (chunk_mode() above) has no such bound and needs the term; in its block mode the term is compiled in
+// and, by this bound, never taken.
 static_assert(kEncodeWaveBytes + 2u <= 0xFFFFFu && kPpwListMaxBlock + 2u <= 0xFFFFFu, "blocks of the list codecs' position-parallel encoders must stay below the reference's 20 bit penalty step");
 
 enum PpwKind : int { PPW_NONE = 0, PPW_8, PPW_L, PPW_S };   // which windowed launcher a row has (CodecLaunch::ppw8, then ppwL, then ppwS)

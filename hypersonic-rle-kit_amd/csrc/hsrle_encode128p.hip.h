@@ -21,7 +21,7 @@
 // run of the body, at most six others).
 #pragma once
 
-#include "hsrle_encode8sp.hip.h"   // pp_put_chunks; hsrle_encodeSp.hip.h: pp_symbol, pp_or_bytes
+#include "hsrle_pp_common.hip.h"
 
 namespace hsrle {
 
@@ -102,15 +102,11 @@ __device__ __forceinline__ void pp128_block(uint64_t U, uint32_t B, uint32_t b, 
     const uint64_t ends = ~m64 & prev;                                     // bit i: a stretch of set bits ends in front of position base + i
     const int32_t ownStart = (starts != 0ull) ? (int32_t)(base + 63u - (uint32_t)__builtin_clzll(starts)) : -1;
     const uint32_t carryStart = wave_shr1((uint32_t)wave_scan_max(ownStart), 0xFFFFFFFFu);
-    auto shl_in = [&](uint64_t v, uint32_t t) __attribute__((always_inline)) -> uint64_t {
-      const uint32_t top = wave_shr1((uint32_t)(v >> 32), 0u);
-      return (v << t) | (uint64_t)(top >> (32u - t));
-    };
-    const uint64_t c2 = m64 & shl_in(m64, 1u);
-    const uint64_t c4 = c2 & shl_in(c2, 2u);
-    const uint64_t c8 = c4 & shl_in(c4, 4u);
-    const uint64_t full = c8 & shl_in(c8, 8u);                              // bit i: the 16 bits up to and including position i are all set
-    const uint64_t cands = ends & shl_in(full, 1u);
+    const uint64_t c2 = m64 & pp_shl_in(m64, 1u, 0u);
+    const uint64_t c4 = c2 & pp_shl_in(c2, 2u, 0u);
+    const uint64_t c8 = c4 & pp_shl_in(c4, 4u, 0u);
+    const uint64_t full = c8 & pp_shl_in(c8, 8u, 0u);                              // bit i: the 16 bits up to and including position i are all set
+    const uint64_t cands = ends & pp_shl_in(full, 1u, 0u);
     const uint32_t cnt = (uint32_t)__builtin_popcountll(cands);
     const uint32_t inclCnt = wave_scan_add(cnt);
     const uint32_t R = wave_lane(inclCnt, 63);

@@ -26,8 +26,7 @@
 // under load against a wave's life of 6: experiments/r05/encode8p_single_pass_lookback.hip.h.txt, LAB_NOTEBOOK.md.
 #pragma once
 
-#include "hsrle_common.hip.h"
-#include "hsrle_decode.hip.h" // lds_read16, wave_sync
+#include "hsrle_pp_common.hip.h"
 
 namespace hsrle {
 
@@ -37,35 +36,6 @@ namespace hsrle {
 #define HS_PSTAMP(slot)
 #endif
 
-// (kPpMaxBlock, kPpRecords: hsrle_common.hip.h -- the host side needs them too)
-constexpr uint32_t kPpNoRecords = 0xFFFFFFFFu;                  // recCount[b]: the block stored more runs than its records hold
-
-// ---- wave-level primitives on DPP (no LDS round trip: a ds_bpermute based __shfl_up costs ~100 cycles of latency per step) ----
-__device__ __forceinline__ uint32_t wave_shr1(uint32_t v, uint32_t fill) { return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x138, 0xF, 0xF, false); }   // lane i <- lane i - 1
-__device__ __forceinline__ uint32_t wave_shl1(uint32_t v, uint32_t fill) { return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x130, 0xF, 0xF, false); }   // lane i <- lane i + 1
-__device__ __forceinline__ uint32_t wave_scan_add(uint32_t v)   // inclusive
-{
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);
-  return v;
-}
-__device__ __forceinline__ int32_t imax(int32_t a, int32_t b) { return a > b ? a : b; }
-__device__ __forceinline__ int32_t wave_scan_max(int32_t v)     // inclusive; values >= -1
-{
-  v = imax(v, __builtin_amdgcn_update_dpp(-1, v, 0x111, 0xF, 0xF, false));
-  v = imax(v, __builtin_amdgcn_update_dpp(-1, v, 0x112, 0xF, 0xF, false));
-  v = imax(v, __builtin_amdgcn_update_dpp(-1, v, 0x114, 0xF, 0xF, false));
-  v = imax(v, __builtin_amdgcn_update_dpp(-1, v, 0x118, 0xF, 0xF, false));
-  v = imax(v, __builtin_amdgcn_update_dpp(-1, v, 0x142, 0xA, 0xF, false));
-  v = imax(v, __builtin_amdgcn_update_dpp(-1, v, 0x143, 0xC, 0xF, false));
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_lane(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
-
 #ifndef HSRLE_PP8_INPUT_LDS
 #define HSRLE_PP8_INPUT_LDS 1   // (round 6: 8 GiB rle8_packed_multi encode 1 727 -> 1 841 GiB/s; 0 = the global gather, A/B builds)
 #endif
@@ -74,49 +44,27 @@ constexpr bool kPp8InputLds = HSRLE_PP8_INPUT_LDS != 0;        // MODE 0: a cand
 #define HSRLE_PP8_BPW 1
 #endif
 constexpr uint32_t kPp8Bpw = HSRLE_PP8_BPW;                      // blocks per wave of k_encode8_pp, the next block's input requested ahead (A/B builds; round 6, 8 GiB: 2 -> 1 745, 4 -> 1 775 GiB/s against 1 836 with one block per wave)
-constexpr uint32_t kPpCoopMin = 80u;                            // literal stretches longer than this are copied by the whole wave, shorter ones by their packet's lane
-constexpr uint32_t kPpJobs = kPpMaxBlock / (kPpCoopMin + 4u) + 2u;
-constexpr uint32_t kPpInPad = 16u;                              // the input image starts 16 bytes into its buffer (a literal window may begin up to 15 bytes in front of its stretch)
-// LDS of one wave's block
-template <bool EMIT, bool INPUT = EMIT, bool MTF = false>
-struct PpShared
-{
-  uint8_t img[EMIT ? (kPpMaxBlock + 193u + 15u + 16u + 15u) / 16u * 16u : 16u] __attribute__((aligned(16)));   // the stream under construction
-  uint8_t inb[INPUT ? kPpInPad + kPpMaxBlock + 32u : 16u] __attribute__((aligned(16)));   // the block's input: literals and run symbols come from here, not from L2 (0.8 us per gather under load)
-  uint8_t mlut[EMIT ? 17u * 16u : 16u] __attribute__((aligned(16)));   // entry c: the low c bytes, c = 0 .. 16
-  uint64_t starts[64];                                                  // run-start bits of every lane's 64 positions
-  uint64_t mtfScratch[MTF ? 152u : 1u];                                 // LUT codecs: the round's run symbols and list heads
-  uint64_t jobs[EMIT ? kPpJobs : 1u];                                   // literal stretches for the whole wave
-  uint16_t lst[64];                                                     // the round's candidates (last byte positions), handed from the lanes that found them to the lanes that judge them
-  uint16_t carryStart[64];                                              // start of the run that is open where a lane's positions begin
-  uint32_t jobCount;
-};
+// what the store rule reads of a candidate run: its start, its length, its symbol, and whether the canonical AVX2 body judges it (not the tail)
+// (a struct of references, as the lambda it replaces captured them: by-value parameters gave the same results and other device code in 3 of 4 kernels.  Change
+//  members only together with tools/device_code_diff.py.)
+struct Pp8Run { const uint32_t &p, &count, &sym; const bool &body; };
 
-// scratch between the two launches
-struct PpScratch
+// the store rule of the block kernel below and of the windowed one (hsrle_encode8pw.hip.h): 0 = not stored, 1 = stored with a one-byte range, 2 = with a 32 bit
+// range.  iL / iY: lastRLE and lastSymbol in front of the run; sm: Packed, the run's symbol is lastSymbol (only the body rule tracks it)
+template <bool PK>
+__device__ __forceinline__ int pp8_decide(const Pp8Run &r, uint32_t iL, uint32_t iY, bool &sm)
 {
-  uint32_t *recs;       // [nBlocks][recStride]   start | (end - 1) << 12 | same << 24 | (32 bit range field) << 25, one per stored run
-  uint32_t *recCount;   // [nBlocks]              stored runs, kPpNoRecords where they did not fit
-  uint32_t recStride;   // pp_record_stride(B)
-  uint8_t *stamps;      // diagnostic builds
-};
-
-// lane l's 64 bytes of block b (zeros behind the end of the input)
-__device__ __forceinline__ void pp_load(const uint8_t *__restrict__ in, uint64_t U, uint32_t B, uint32_t b, u32x4 (&x)[4])
-{
-  const uint64_t at = (uint64_t)b * B;
-  const uint32_t n = (uint32_t)((U - at) < (uint64_t)B ? (U - at) : (uint64_t)B);
-  const uint8_t *const d = in + at;
-  const uint32_t base = threadIdx.x * 64u;
-#pragma unroll
-  for (uint32_t j = 0; j < 4u; j++)
+  const uint32_t rng = r.p - iL + 1u;
+  sm = false;
+  if constexpr (PK)
   {
-    const uint32_t pos = base + 16u * j;
-    u32x4 v = u32x4{ 0, 0, 0, 0 };
-    if (pos + 16u <= n) v = ld128(d + pos);
-    else if (pos < n) v = load16_edge(d, (int64_t)pos, (uint64_t)n);
-    x[j] = v;
+    if (!r.body) return (r.count >= 11u) ? (rng <= 127u ? 1 : 2) : 0;
+    sm = r.sym == iY;
+    const bool emit = r.count >= 11u || (rng <= 127u && ((sm && r.count >= 3u) || r.count >= 4u));     // rle8_extreme_cpu.h:978
+    return emit ? (rng <= 127u ? 1 : 2) : 0;
   }
+  else
+    return (r.count >= 6u) ? (rng <= 255u ? 1 : 2) : 0;                                                   // :974
 }
 
 // one block by one wave.  MODE 0: sizes[b] and the block's records; MODE 1: the stream, written to payload + offsets[b].  rec0: the block's first 64
@@ -208,29 +156,6 @@ __device__ __forceinline__ void pp_block(const uint8_t *__restrict__ in, uint64_
   }
   wave_sync();
 
-  // literal bytes [src, src + len) of the block -> image bytes [ds, ds + len), the destination chunks t0, t0 + tStep, ... below tEnd of the stretch
-  // by this lane: a 16-byte window of the input image placed so that every byte lands where it belongs (two aligned LDS reads + a byte funnel),
-  // cut to the stretch under two byte masks, OR-ed into the image
-  [[maybe_unused]] auto put_chunks = [&](uint32_t src, uint32_t ds, uint32_t len, uint32_t t0, uint32_t tStep, uint32_t tEnd) __attribute__((always_inline)) {
-    const uint32_t de = ds + len, D0 = ds & ~15u;
-    for (uint32_t t = t0; t < tEnd; t += tStep)
-    {
-      const uint32_t D = D0 + 16u * t;
-      // (D - ds may be "negative": the pad in front of the image absorbs it.)  Five dwords from the dword below the window + four v_alignbyte: dword
-      // reads need no 16-byte alignment, and the 16-byte form (two aligned reads + a select funnel) was 15 vector instructions of the chunk's 35
-      const uint32_t wa = kPpInPad + src + D - ds;
-      const uint32_t *const wq = (const uint32_t *)(sh.inb + (wa & ~3u));
-      const uint32_t q0 = wq[0], q1 = wq[1], q2 = wq[2], q3 = wq[3], q4 = wq[4], sb = wa & 3u;
-      const u32x4 v = u32x4{ alignbyte(q1, q0, sb), alignbyte(q2, q1, sb), alignbyte(q3, q2, sb), alignbyte(q4, q3, sb) };
-      const uint32_t lo = D < ds ? ds - D : 0u, hi = de - D < 16u ? de - D : 16u;      // chunk bytes [lo, hi)
-      const u32x4 mh = lds_ld128(sh.mlut + (hi << 4)), ml = lds_ld128(sh.mlut + (lo << 4));
-      unsigned long long *const ip = (unsigned long long *)(sh.img + D);
-      const uint64_t w0 = (uint64_t)(v.x & mh.x & ~ml.x) | ((uint64_t)(v.y & mh.y & ~ml.y) << 32), w1 = (uint64_t)(v.z & mh.z & ~ml.z) | ((uint64_t)(v.w & mh.w & ~ml.w) << 32);
-      atomicOr(ip, w0);
-      atomicOr(ip + 1, w1);
-    }
-  };
-
   HS_PSTAMP(2)
   // ---- 2. one candidate (or record) per lane, 64 per round ----
   uint32_t carL = 0, carY = 0;                       // state in front of the round's first candidate
@@ -282,19 +207,7 @@ __device__ __forceinline__ void pp_block(const uint8_t *__restrict__ in, uint64_
       }
       HS_PSTAMP(8)
       const bool sure = have && count >= LONGC;
-      auto decide = [&](uint32_t iL, uint32_t iY, bool &sm) __attribute__((always_inline)) -> int {
-        const uint32_t rng = p - iL + 1u;
-        sm = false;
-        if constexpr (PK)
-        {
-          if (!body) return (count >= 11u) ? (rng <= 127u ? 1 : 2) : 0;
-          sm = sym == iY;
-          const bool emit = count >= 11u || (rng <= 127u && ((sm && count >= 3u) || count >= 4u));     // rle8_extreme_cpu.h:978
-          return emit ? (rng <= 127u ? 1 : 2) : 0;
-        }
-        else
-          return (count >= 6u) ? (rng <= 255u ? 1 : 2) : 0;                                               // :974
-      };
+      const Pp8Run run{ p, count, sym, body };
       uint32_t outY = sym, inY = 0;
       outL = e;
       bool outKnown = sure || !have, inKnown = !have;
@@ -305,14 +218,14 @@ __device__ __forceinline__ void pp_block(const uint8_t *__restrict__ in, uint64_
         if (inKnown && !outKnown)
         {
           bool sm;
-          if (decide(inL, inY, sm) == 0) { outL = inL; outY = inY; }
+          if (pp8_decide<PK>(run, inL, inY, sm) == 0) { outL = inL; outY = inY; }
           else if (PK && !body) outY = inY;                                // (only the body rule tracks lastSymbol)
           outKnown = true;
         }
         if (__ballot(!inKnown) == 0ull) break;
       }
       HS_PSTAMP(9)
-      k = have ? decide(inL, inY, same) : 0;
+      k = have ? pp8_decide<PK>(run, inL, inY, same) : 0;
       carY = wave_lane(outY, lastLane);
     }
     const uint32_t count = e - p, gap = p - inL, rng = gap + 1u;
@@ -395,8 +308,8 @@ __device__ __forceinline__ void pp_block(const uint8_t *__restrict__ in, uint64_
       }
       for (uint32_t t = 0; __ballot(t < nch) != 0ull; t += 2u)            // (the lanes together, two chunks per trip in flight)
       {
-        if (t < nch) put_chunks(inL, ds, gap, t, 1u, t + 1u);
-        if (t + 1u < nch) put_chunks(inL, ds, gap, t + 1u, 1u, t + 2u);
+        if (t < nch) pp_put_chunks(sh, inL, ds, gap, t, 1u, t + 1u);
+        if (t + 1u < nch) pp_put_chunks(sh, inL, ds, gap, t + 1u, 1u, t + 2u);
       }
     }
     HS_PSTAMP(11)
@@ -449,7 +362,7 @@ __device__ __forceinline__ void pp_block(const uint8_t *__restrict__ in, uint64_
         uint32_t src, ds, len;
         if (j < nj) { const uint64_t jb = sh.jobs[j]; src = (uint32_t)jb & 0x1FFFu; ds = (uint32_t)(jb >> 13) & 0x1FFFu; len = (uint32_t)(jb >> 26); }
         else { src = carL; ds = pos + TERM; len = kLit; }
-        if (len != 0u) put_chunks(src, ds, len, lane, 64u, ((ds + len - 1u) >> 4) - (ds >> 4) + 1u);
+        if (len != 0u) pp_put_chunks(sh, src, ds, len, lane, 64u, ((ds + len - 1u) >> 4) - (ds >> 4) + 1u);
       }
     }
     wave_sync();
@@ -478,15 +391,7 @@ __global__ __launch_bounds__(64) void k_encode8_pp(const uint8_t *__restrict__ i
   __shared__ PpShared<MODE != 0, kPp8InputLds || MODE != 0> sh;
   if constexpr (MODE != 0)
   {
-    if (threadIdx.x < 17u)
-    {
-      // merge masks: entry c = the low c bytes (as in k_decode_blocks; entry 16: all of them)
-      const uint32_t c = threadIdx.x;
-      const uint64_t part = ~(~0ull << (8u * (c & 7u)));
-      const bool hiHalf = c >= 8u;
-      const uint32_t p0 = (c == 16u) ? ~0u : (uint32_t)part, p1 = (c == 16u) ? ~0u : (uint32_t)(part >> 32);
-      lds_st128(sh.mlut + c * 16u, u32x4{ hiHalf ? ~0u : p0, hiHalf ? ~0u : p1, hiHalf ? p0 : 0u, hiHalf ? p1 : 0u });
-    }
+    pp_init_mlut(sh.mlut);
     wave_sync();
   }
   if constexpr (kPp8Bpw == 1u)

@@ -22,29 +22,6 @@ namespace hsrle {
 
 // (PpwArgs, kPpwWindow / kPpwStateWords / kPpwStride / kPpwEmpty, ppw_scratch_bytes: hsrle_launch.h -- the host side needs them too)
 
-// lane l's 64 bytes of the window at `ws` of a unit of n bytes (zeros behind its end)
-__device__ __forceinline__ void ppw_load(const uint8_t *__restrict__ d, uint32_t n, uint32_t ws, u32x4 (&x)[4])
-{
-  const uint32_t base = ws + threadIdx.x * 64u;
-#pragma unroll
-  for (uint32_t j = 0; j < 4u; j++)
-  {
-    const uint32_t pos = base + 16u * j;
-    u32x4 v = u32x4{ 0, 0, 0, 0 };
-    if (pos + 16u <= n) v = ld128(d + pos);
-    else if (pos < n) v = load16_edge(d, (int64_t)pos, (uint64_t)n);
-    x[j] = v;
-  }
-}
-
-// 16 image bytes from any offset (dword reads + a byte funnel: LDS dword reads need no 16-byte alignment)
-__device__ __forceinline__ u32x4 ppw_img16(const uint8_t *img, uint32_t off)
-{
-  const uint32_t *const q = (const uint32_t *)(img + (off & ~3u));
-  const uint32_t q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], sb = off & 3u;
-  return u32x4{ alignbyte(q1, q0, sb), alignbyte(q2, q1, sb), alignbyte(q3, q2, sb), alignbyte(q4, q3, sb) };
-}
-
 // One window by one wave.  d / n / nT: the unit's bytes, its length, the bytes from its start to the end of the stream's input (the Packed body / tail rule
 // looks at the input's end).  carL / carY / pos / openStart / ended: the state in front of the window, and behind it on return (MODE 0).
 // MODE 0: the window's state + records; MODE 1: its packets -> dst (= the unit's stream) + pos.
@@ -129,25 +106,6 @@ __device__ __forceinline__ void ppw_window(const uint8_t *__restrict__ d, uint32
   }
   wave_sync();
 
-  [[maybe_unused]] auto put_chunks = [&](uint32_t src, uint32_t ds, uint32_t len, uint32_t t0, uint32_t tStep, uint32_t tEnd) __attribute__((always_inline)) {
-    // literal bytes [src, src + len) of the WINDOW -> image bytes [ds, ds + len) (hsrle_encode8p.hip.h)
-    const uint32_t de = ds + len, D0 = ds & ~15u;
-    for (uint32_t t = t0; t < tEnd; t += tStep)
-    {
-      const uint32_t D = D0 + 16u * t;
-      const uint32_t wa = kPpInPad + src + D - ds;
-      const uint32_t *const wq = (const uint32_t *)(sh.inb + (wa & ~3u));
-      const uint32_t q0 = wq[0], q1 = wq[1], q2 = wq[2], q3 = wq[3], q4 = wq[4], sb = wa & 3u;
-      const u32x4 v = u32x4{ alignbyte(q1, q0, sb), alignbyte(q2, q1, sb), alignbyte(q3, q2, sb), alignbyte(q4, q3, sb) };
-      const uint32_t lo = D < ds ? ds - D : 0u, hi = de - D < 16u ? de - D : 16u;
-      const u32x4 mh = lds_ld128(sh.mlut + (hi << 4)), ml = lds_ld128(sh.mlut + (lo << 4));
-      unsigned long long *const ip = (unsigned long long *)(sh.img + D);
-      const uint64_t w0 = (uint64_t)(v.x & mh.x & ~ml.x) | ((uint64_t)(v.y & mh.y & ~ml.y) << 32), w1 = (uint64_t)(v.z & mh.z & ~ml.z) | ((uint64_t)(v.w & mh.w & ~ml.w) << 32);
-      atomicOr(ip, w0);
-      atomicOr(ip + 1, w1);
-    }
-  };
-
   // ---- 2. one candidate (or record) per lane, 64 per round ----
   uint32_t imgPos = (hasHeader && w == 0u) ? 9u : 0u;  // MODE 1: image position of the round's first packet
   uint32_t K = 0;                                      // stored runs of this window
@@ -199,19 +157,7 @@ __device__ __forceinline__ void ppw_window(const uint8_t *__restrict__ d, uint32
         body = (e < nT) && ((int64_t)p + 1 + 32 * kk < (int64_t)nT - 32);
       }
       const bool sure = have && count >= LONGC;
-      auto decide = [&](uint32_t iL, uint32_t iY, bool &sm) __attribute__((always_inline)) -> int {
-        const uint32_t rng = p - iL + 1u;
-        sm = false;
-        if constexpr (PK)
-        {
-          if (!body) return (count >= 11u) ? (rng <= 127u ? 1 : 2) : 0;
-          sm = sym == iY;
-          const bool emit = count >= 11u || (rng <= 127u && ((sm && count >= 3u) || count >= 4u));     // rle8_extreme_cpu.h:978
-          return emit ? (rng <= 127u ? 1 : 2) : 0;
-        }
-        else
-          return (count >= 6u) ? (rng <= 255u ? 1 : 2) : 0;                                               // :974
-      };
+      const Pp8Run run{ p, count, sym, body };
       uint32_t outY = sym, inY = 0;
       outL = e;
       bool outKnown = sure || !have, inKnown = !have;
@@ -222,13 +168,13 @@ __device__ __forceinline__ void ppw_window(const uint8_t *__restrict__ d, uint32
         if (inKnown && !outKnown)
         {
           bool sm;
-          if (decide(inL, inY, sm) == 0) { outL = inL; outY = inY; }
+          if (pp8_decide<PK>(run, inL, inY, sm) == 0) { outL = inL; outY = inY; }
           else if (PK && !body) outY = inY;
           outKnown = true;
         }
         if (__ballot(!inKnown) == 0ull) break;
       }
-      k = have ? decide(inL, inY, same) : 0;
+      k = have ? pp8_decide<PK>(run, inL, inY, same) : 0;
       carY = wave_lane(outY, lastLane);
     }
     const uint32_t count = e - p, gap = p - inL, rng = gap + 1u;
@@ -326,8 +272,8 @@ __device__ __forceinline__ void ppw_window(const uint8_t *__restrict__ d, uint32
       }
       for (uint32_t t = 0; __ballot(t < nch) != 0ull; t += 2u)
       {
-        if (t < nch) put_chunks(inLw - ws, ds, gapImg, t, 1u, t + 1u);
-        if (t + 1u < nch) put_chunks(inLw - ws, ds, gapImg, t + 1u, 1u, t + 2u);
+        if (t < nch) pp_put_chunks(sh, inLw - ws, ds, gapImg, t, 1u, t + 1u);
+        if (t + 1u < nch) pp_put_chunks(sh, inLw - ws, ds, gapImg, t + 1u, 1u, t + 2u);
       }
       imgPos += wave_lane(incl, 63);
     }
@@ -391,7 +337,7 @@ __device__ __forceinline__ void ppw_window(const uint8_t *__restrict__ d, uint32
         uint32_t src, ds, len;
         if (j < nj) { const uint64_t jb = sh.jobs[j]; src = (uint32_t)jb & 0x1FFFu; ds = (uint32_t)(jb >> 13) & 0x1FFFu; len = (uint32_t)(jb >> 26); }
         else { src = tailSrc; ds = imgPos + TERM; len = tailLen; }
-        if (len != 0u) put_chunks(src, ds, len, lane, 64u, ((ds + len - 1u) >> 4) - (ds >> 4) + 1u);
+        if (len != 0u) pp_put_chunks(sh, src, ds, len, lane, 64u, ((ds + len - 1u) >> 4) - (ds >> 4) + 1u);
       }
     }
     wave_sync();
@@ -495,14 +441,7 @@ template <int FAM>
 __global__ __launch_bounds__(64) void k_encode8_ppw_emit(PpwArgs a)
 {
   __shared__ PpShared<true, true> sh;
-  if (threadIdx.x < 17u)
-  {
-    const uint32_t c = threadIdx.x;
-    const uint64_t part = ~(~0ull << (8u * (c & 7u)));
-    const bool hiHalf = c >= 8u;
-    const uint32_t p0 = (c == 16u) ? ~0u : (uint32_t)part, p1 = (c == 16u) ? ~0u : (uint32_t)(part >> 32);
-    lds_st128(sh.mlut + c * 16u, u32x4{ hiHalf ? ~0u : p0, hiHalf ? ~0u : p1, hiHalf ? p0 : 0u, hiHalf ? p1 : 0u });
-  }
+  pp_init_mlut(sh.mlut);
   const uint32_t gw = xcd_tile(blockIdx.x, gridDim.x);
   if (gw >= a.nWindows) return;
   const uint32_t *const st = a.states + (uint64_t)gw * kPpwStateWords;

@@ -25,7 +25,7 @@
 // literals from the records into an LDS image of the stream and writes it once.
 #pragma once
 
-#include "hsrle_encodeSp.hip.h"   // pp_or_bytes; hsrle_encode8p.hip.h: the DPP primitives, PpScratch, pp_load
+#include "hsrle_pp_common.hip.h"
 
 namespace hsrle {
 
@@ -45,27 +45,6 @@ struct PpSingleShared
   uint16_t carryStart[64];                                              // start of the run that is open where a lane's positions begin
   uint32_t jobCount;
 };
-
-// literal bytes [src, src + len) of the block -> image bytes [ds, ds + len): the destination chunks t0, t0 + tStep, ... below tEnd (hsrle_encode8p.hip.h: put_chunks)
-template <class SH>
-__device__ __forceinline__ void pp_put_chunks(SH &sh, uint32_t src, uint32_t ds, uint32_t len, uint32_t t0, uint32_t tStep, uint32_t tEnd)
-{
-  const uint32_t de = ds + len, D0 = ds & ~15u;
-  for (uint32_t t = t0; t < tEnd; t += tStep)
-  {
-    const uint32_t D = D0 + 16u * t;
-    const uint32_t wa = kPpInPad + src + D - ds;
-    const uint32_t *const wq = (const uint32_t *)(sh.inb + (wa & ~3u));
-    const uint32_t q0 = wq[0], q1 = wq[1], q2 = wq[2], q3 = wq[3], q4 = wq[4], sb = wa & 3u;
-    const u32x4 v = u32x4{ alignbyte(q1, q0, sb), alignbyte(q2, q1, sb), alignbyte(q3, q2, sb), alignbyte(q4, q3, sb) };
-    const uint32_t lo = D < ds ? ds - D : 0u, hi = de - D < 16u ? de - D : 16u;      // chunk bytes [lo, hi)
-    const u32x4 mh = lds_ld128(sh.mlut + (hi << 4)), ml = lds_ld128(sh.mlut + (lo << 4));
-    unsigned long long *const ip = (unsigned long long *)(sh.img + D);
-    const uint64_t w0 = (uint64_t)(v.x & mh.x & ~ml.x) | ((uint64_t)(v.y & mh.y & ~ml.y) << 32), w1 = (uint64_t)(v.z & mh.z & ~ml.z) | ((uint64_t)(v.w & mh.w & ~ml.w) << 32);
-    atomicOr(ip, w0);
-    atomicOr(ip + 1, w1);
-  }
-}
 
 // the block's symbol (rle8_extreme_cpu.c:53-153 as k_single_pick's closed form): x = this lane's 64 bytes, the input image is in sh.inb
 template <bool EMIT>

@@ -19,7 +19,7 @@
 //     without such candidates (nearly all of the synthetic data) take one iteration.  Symbols of >= 3 bytes: every run is stored (count >= 2 S >= 6).
 #pragma once
 
-#include "hsrle_encode8sp.hip.h"   // pp_put_chunks; hsrle_encodeSp.hip.h: pp_symbol, pp_or_bytes
+#include "hsrle_pp_common.hip.h"
 
 namespace hsrle {
 
@@ -137,26 +137,22 @@ __device__ __forceinline__ void ppL_block(uint64_t U, uint32_t B, uint32_t b, ui
     const uint64_t ends = ~m64 & prev;
     const int32_t ownStart = (starts != 0ull) ? (int32_t)(base + 63u - (uint32_t)__builtin_clzll(starts)) : -1;
     const uint32_t carryStart = wave_shr1((uint32_t)wave_scan_max(ownStart), 0xFFFFFFFFu);
-    auto shl_in = [&](uint64_t v, uint32_t t) __attribute__((always_inline)) -> uint64_t {
-      const uint32_t top = wave_shr1((uint32_t)(v >> 32), 0u);
-      return (v << t) | (uint64_t)(top >> (32u - t));
-    };
     // candidates: the stretches of at least S bits; 8 bit: of at least 2 (a run of two bytes is never stored: count >= 3 + penalty)
     uint64_t full;
     {
-      const uint64_t c2 = m64 & shl_in(m64, 1u);
+      const uint64_t c2 = m64 & pp_shl_in(m64, 1u, 0u);
       if constexpr (S == 1 && SH) full = m64;                            // (Short: a run of two bytes of a listed symbol right behind the run before is stored)
       else if constexpr (S <= 2) full = c2;
-      else if constexpr (S == 3) full = c2 & shl_in(m64, 2u);
+      else if constexpr (S == 3) full = c2 & pp_shl_in(m64, 2u, 0u);
       else
       {
-        const uint64_t c4 = c2 & shl_in(c2, 2u);
+        const uint64_t c4 = c2 & pp_shl_in(c2, 2u, 0u);
         if constexpr (S == 4) full = c4;
-        else if constexpr (S == 6) full = c4 & shl_in(c2, 4u);
-        else full = c4 & shl_in(c4, 4u);
+        else if constexpr (S == 6) full = c4 & pp_shl_in(c2, 4u, 0u);
+        else full = c4 & pp_shl_in(c4, 4u, 0u);
       }
     }
-    const uint64_t cands = ends & shl_in(full, 1u);
+    const uint64_t cands = ends & pp_shl_in(full, 1u, 0u);
     const uint32_t cnt = (uint32_t)__builtin_popcountll(cands);
     const uint32_t inclCnt = wave_scan_add(cnt);
     R = wave_lane(inclCnt, 63);
@@ -214,25 +210,15 @@ __device__ __forceinline__ void ppL_block(uint64_t U, uint32_t B, uint32_t b, ui
       bool geoKnown = !have || (lane != 0u ? s0 >= qLeft + SU : s0 >= carE);
       uint32_t outE = 0;
       bool outEKnown = false;
-      auto run_from = [&](uint32_t resume) __attribute__((always_inline)) {
-        const uint32_t ps = resume > s0 ? resume : s0;
-        p = ps; e = 0u;
-        if (have && q >= ps + SU)
-        {
-          const uint32_t Leff = q - ps;
-          const uint32_t whole = ((Leff + SU) / SU) * SU;
-          const uint32_t eW = ps + whole;
-          e = (!AL && eW + SU <= n) ? q + SU : eW;
-        }
-      };
-      if (geoKnown) { run_from(0u); outE = e; outEKnown = have && e != 0u; }
+      const PpStretch stretch{ s0, p, e, have, q, n };
+      if (geoKnown) { pp_run_from<S, AL>(stretch, 0u); outE = e; outEKnown = have && e != 0u; }
       if (!have) { outEKnown = true; outE = 0u; }
       for (uint32_t pass = 0; pass < 66u; pass++)
       {
         const uint32_t lk = wave_shr1(outEKnown ? 1u : 0u, 1u), le = wave_shr1(outE, carE);
         if (have && !outEKnown && lk != 0u)
         {
-          if (!geoKnown) { run_from(le); geoKnown = true; }
+          if (!geoKnown) { pp_run_from<S, AL>(stretch, le); geoKnown = true; }
           outE = (e != 0u) ? e : le;
           outEKnown = true;
         }
@@ -635,14 +621,7 @@ __global__ __launch_bounds__(64) void k_encodeL_pp(const uint8_t *__restrict__ i
                                                    const uint64_t *__restrict__ offsets, uint8_t *__restrict__ payload, PpScratch sc)
 {
   __shared__ PpLutShared<MODE != 0, ((FAM == LUT3 || FAM == SHORT3) ? 3 : 7)> sh;
-  if (MODE != 0 && threadIdx.x < 17u)
-  {
-    const uint32_t c = threadIdx.x;
-    const uint64_t part = ~(~0ull << (8u * (c & 7u)));
-    const bool hiHalf = c >= 8u;
-    const uint32_t p0 = (c == 16u) ? ~0u : (uint32_t)part, p1 = (c == 16u) ? ~0u : (uint32_t)(part >> 32);
-    lds_st128(sh.mlut + c * 16u, u32x4{ hiHalf ? ~0u : p0, hiHalf ? ~0u : p1, hiHalf ? p0 : 0u, hiHalf ? p1 : 0u });
-  }
+  if (MODE != 0) pp_init_mlut(sh.mlut);
   wave_sync();
   const uint32_t b = xcd_tile(blockIdx.x, gridDim.x);
   if (b < nBlocks)

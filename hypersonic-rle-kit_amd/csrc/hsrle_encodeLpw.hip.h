@@ -13,7 +13,6 @@
 #pragma once
 
 #include "hsrle_encodeLp.hip.h"
-#include "hsrle_encodeSpw.hip.h"   // hsrle_encode8pw.hip.h: ppw_load, ppw_img16
 
 namespace hsrle {
 
@@ -83,13 +82,6 @@ __device__ __forceinline__ void ppLw_window(const uint8_t *__restrict__ d, uint3
   if (lane == 0u) lds_st128(sh.inb, front);
   if (lane == 63u) { lds_st128(sh.inb + kPpInPad + kPpMaxBlock, back0); lds_st128(sh.inb + kPpInPad + kPpMaxBlock + 16u, zero4); }
 
-  // the S-byte symbol of the run that starts at p (absolute) and reaches into this window
-  auto symbol_at = [&](uint32_t p) __attribute__((always_inline)) -> uint64_t {
-    uint32_t a = p;
-    if (ws >= 16u && p < ws - 16u) a = p + ((ws - 16u - p + SU - 1u) / SU) * SU;      // (a later period of the run)
-    return pp_symbol<S>(sh.inb, kPpInPad + a - ws);
-  };
-
   // ---- 1. match bits m[j] = (d[j] == d[j + S]), stretches, candidates (hsrle_encodeSpw.hip.h) ----
   uint32_t R = recN;
   uint64_t candLeft = 0;
@@ -146,27 +138,23 @@ __device__ __forceinline__ void ppLw_window(const uint8_t *__restrict__ d, uint3
     const int32_t ownStart = (starts != 0ull) ? (int32_t)(base + 63u - (uint32_t)__builtin_clzll(starts)) : -1;
     const int32_t inclStart = wave_scan_max(ownStart);
     const uint32_t carryStart = wave_shr1((uint32_t)inclStart, 0xFFFFFFFFu);
-    auto shl_in = [&](uint64_t v, uint32_t t, uint32_t hist) __attribute__((always_inline)) -> uint64_t {
-      const uint32_t top = wave_shr1((uint32_t)(v >> 32), hist);
-      return (v << t) | (uint64_t)(top >> (32u - t));
-    };
     // candidates: the stretches of at least S bits; 8 bit: of at least 2 (Short: of 1 -- a run of two bytes of a listed symbol right behind the run before is stored)
     uint64_t full;
     uint32_t histFull;
     {
-      const uint64_t c2 = m64 & shl_in(m64, 1u, histM);
+      const uint64_t c2 = m64 & pp_shl_in(m64, 1u, histM);
       if constexpr (S == 1 && SH) { full = m64; histFull = histM; }
       else if constexpr (S <= 2) { full = c2; histFull = histC2; }
-      else if constexpr (S == 3) { full = c2 & shl_in(m64, 2u, histM); histFull = histC2 & (histM << 2); }
+      else if constexpr (S == 3) { full = c2 & pp_shl_in(m64, 2u, histM); histFull = histC2 & (histM << 2); }
       else
       {
-        const uint64_t c4 = c2 & shl_in(c2, 2u, histC2);
+        const uint64_t c4 = c2 & pp_shl_in(c2, 2u, histC2);
         if constexpr (S == 4) { full = c4; histFull = histC4; }
-        else if constexpr (S == 6) { full = c4 & shl_in(c2, 4u, histC2); histFull = histC4 & (histC2 << 4); }
-        else { full = c4 & shl_in(c4, 4u, histC4); histFull = histC4 & (histC4 << 4); }
+        else if constexpr (S == 6) { full = c4 & pp_shl_in(c2, 4u, histC2); histFull = histC4 & (histC2 << 4); }
+        else { full = c4 & pp_shl_in(c4, 4u, histC4); histFull = histC4 & (histC4 << 4); }
       }
     }
-    const uint64_t cands = ends & shl_in(full, 1u, histFull);
+    const uint64_t cands = ends & pp_shl_in(full, 1u, histFull);
     const uint32_t cnt = (uint32_t)__builtin_popcountll(cands);
     const uint32_t inclCnt = wave_scan_add(cnt);
     R = wave_lane(inclCnt, 63);
@@ -209,7 +197,7 @@ __device__ __forceinline__ void ppLw_window(const uint8_t *__restrict__ d, uint3
       k = have ? 1 : 0;
       outL = e;
       inL = wave_shr1(outL, carL);
-      sym = symbol_at(have ? p : ws);
+      sym = ppw_symbol_at<S>(sh, ws, have ? p : ws);
     }
     else
     {
@@ -239,25 +227,15 @@ __device__ __forceinline__ void ppLw_window(const uint8_t *__restrict__ d, uint3
       bool geoKnown = !have || (lane != 0u ? s0 >= qLeft + SU : s0 >= carE);
       uint32_t outE = 0;
       bool outEKnown = false;
-      auto run_from = [&](uint32_t resume) __attribute__((always_inline)) {
-        const uint32_t ps = resume > s0 ? resume : s0;
-        p = ps; e = 0u;
-        if (have && q >= ps + SU)
-        {
-          const uint32_t Leff = q - ps;
-          const uint32_t whole = ((Leff + SU) / SU) * SU;
-          const uint32_t eW = ps + whole;
-          e = (!AL && eW + SU <= n) ? q + SU : eW;
-        }
-      };
-      if (geoKnown) { run_from(0u); outE = e; outEKnown = have && e != 0u; }
+      const PpStretch stretch{ s0, p, e, have, q, n };
+      if (geoKnown) { pp_run_from<S, AL>(stretch, 0u); outE = e; outEKnown = have && e != 0u; }
       if (!have) { outEKnown = true; outE = 0u; }
       for (uint32_t pass = 0; pass < 66u; pass++)
       {
         const uint32_t lk = wave_shr1(outEKnown ? 1u : 0u, 1u), le = wave_shr1(outE, carE);
         if (have && !outEKnown && lk != 0u)
         {
-          if (!geoKnown) { run_from(le); geoKnown = true; }
+          if (!geoKnown) { pp_run_from<S, AL>(stretch, le); geoKnown = true; }
           outE = (e != 0u) ? e : le;
           outEKnown = true;
         }
@@ -266,7 +244,7 @@ __device__ __forceinline__ void ppLw_window(const uint8_t *__restrict__ d, uint3
       carE = wave_lane(outE, lastLane);
       const bool isRun = have && e != 0u;
       const uint32_t count = e - p;
-      sym = symbol_at(isRun ? p : ws);
+      sym = ppw_symbol_at<S>(sh, ws, isRun ? p : ws);
 
       // EXACT MODE (data over a small alphabet: long stretches of the list's own symbols; entered when the K predecessors do not settle a lane, and for the
       // list behind the round).  One trip per DISTINCT stored symbol of the round (few, where this is needed): the lanes that store it as a ballot -> every
@@ -747,14 +725,7 @@ __global__ __launch_bounds__(64) void k_encodeL_ppw_emit(PpwArgs a)
 {
   constexpr int K = (FAM == LUT3 || FAM == SHORT3) ? 3 : 7;
   __shared__ PpLutShared<true, K> sh;
-  if (threadIdx.x < 17u)
-  {
-    const uint32_t c = threadIdx.x;
-    const uint64_t part = ~(~0ull << (8u * (c & 7u)));
-    const bool hiHalf = c >= 8u;
-    const uint32_t p0 = (c == 16u) ? ~0u : (uint32_t)part, p1 = (c == 16u) ? ~0u : (uint32_t)(part >> 32);
-    lds_st128(sh.mlut + c * 16u, u32x4{ hiHalf ? ~0u : p0, hiHalf ? ~0u : p1, hiHalf ? p0 : 0u, hiHalf ? p1 : 0u });
-  }
+  pp_init_mlut(sh.mlut);
   const uint32_t gw = xcd_tile(blockIdx.x, gridDim.x);
   if (gw >= a.nWindows) return;
   // (which block and window this is follows from the window's number: the state, the first records and the input are asked for together)

@@ -16,37 +16,44 @@
 // in the same DPP passes that settle the emit decisions.
 #pragma once
 
-#include "hsrle_encode8p.hip.h"
+#include "hsrle_pp_common.hip.h"
 
 namespace hsrle {
 
-// the S-byte symbol at LDS byte position `at` of the input image (dwords beyond S bytes zero)
-template <int S>
-__device__ __forceinline__ uint64_t pp_symbol(const uint8_t *inb, uint32_t at)
-{
-  const uint32_t *const w = (const uint32_t *)(inb + (at & ~3u));
-  const uint32_t sb = at & 3u;
-  const uint32_t q0 = w[0], q1 = w[1];
-  uint32_t lo = alignbyte(q1, q0, sb), hi = 0u;
-  if constexpr (S > 4) { const uint32_t q2 = w[2]; hi = alignbyte(q2, q1, sb); }
-  if constexpr (S == 1) lo &= 0xFFu;
-  if constexpr (S == 2) lo &= 0xFFFFu;
-  if constexpr (S == 3) lo &= 0xFFFFFFu;
-  if constexpr (S == 6) hi &= 0xFFFFu;
-  return (uint64_t)lo | ((uint64_t)hi << 32);
-}
+// what the store rule reads of a candidate run: its start, its length, its symbol
+// (member order = the order in which ppS_decide first uses them, as the lambda it replaces captured them: see PpStretch, hsrle_pp_common.hip.h)
+struct PpSRun { const uint32_t &p; const uint64_t &sym; const uint32_t &count; };
 
-// OR the low nb (1 .. 8) bytes of v into the stream image at byte position `at` (LDS atomics on the dwords it touches)
-__device__ __forceinline__ void pp_or_bytes(uint8_t *img, uint32_t at, uint64_t v, uint32_t nb)
+// the store rule of the block kernel below and of the windowed one (hsrle_encodeSpw.hip.h): 0 = not stored, 1 = the short form, 2 = the long one.  iL / iY:
+// lastRLE and the last stored symbol in front of the run; sm: the run's symbol is that symbol (Packed, Short with a one-symbol list).
+// WIDE: a count or range can reach the reference's 20 bit penalty step.  The block kernel says false (a block has at most 4 KiB); the windowed kernel says true, for
+// its blocks of any size and for the chunks of a monolithic stream, which have no length limit.  (The list kernels, hsrle_encodeLp / Lpw .hip.h, never carry the
+// term: the host keeps their blocks below it -- hsrle_codecs.h, the static_assert beside kPpwListMaxBlock.)
+template <int FAM, int S, int AL, bool WIDE>
+__device__ __forceinline__ int ppS_decide(const PpSRun &r, uint32_t iL, uint64_t iY, bool &sm)
 {
-  if (nb < 8u) v &= (1ull << (8u * nb)) - 1ull;
-  uint32_t *const wp = (uint32_t *)(img + (at & ~3u));
-  const uint32_t sh = 8u * (at & 3u);
-  const uint64_t lo = v << sh;
-  const uint32_t top = sh ? (uint32_t)(v >> (64u - sh)) : 0u;          // what the shift pushed beyond 64 bits
-  atomicOr(wp, (uint32_t)lo);
-  if ((uint32_t)(lo >> 32) != 0u) atomicOr(wp + 1, (uint32_t)(lo >> 32));
-  if (top != 0u) atomicOr(wp + 2, top);
+  using TR = Traits<FAM, S, AL>;
+  constexpr bool SH = FAM == SHORT0 || FAM == SHORT1 || FAM == SHORT3, SH1 = FAM == SHORT1, SH3 = FAM == SHORT3, PK = FAM == PACKED, LUT = FAM == LUT3;
+  constexpr uint32_t SU = (uint32_t)S;
+  if constexpr (LUT) { sm = false; return 1; }
+  if constexpr (SH)
+  {
+    // process_symbol of the Short family (rleX_Xsl_short.h:152-215): the packet's size over the one-byte form is a penalty on the shortest run stored;
+    // 1: one-byte header, 2: the 3-byte form (with 16 / 32 bit fields behind it where count or range need them)
+    const uint32_t gp = r.p - iL, range = gp + 2u;
+    sm = SH1 && r.sym == iY;
+    const uint32_t scu = AL ? r.count / SU - TR::SMINS / SU + 2u : r.count - TR::SMINS + 2u;
+    const bool pack1 = gp <= TR::SMAXPR && scu - 2u <= TR::SMAXPC;
+    uint32_t pen = (SH1 && !sm) ? SU : 0u;
+    // (a field behind the 3-byte form costs 2 and, rleX_Xsl_short.h:197, above 20 bits 4 -- the term that only WIDE carries)
+    if (!pack1) pen += 2u + ((!WIDE || range <= 0xFFFFFu) ? (range <= TR::SMAXTR ? 0u : 2u) : 4u) + ((!WIDE || scu <= 0xFFFFFu) ? (scu <= TR::SMAXTC ? 0u : 2u) : 4u);
+    if (!SH3 && !(r.count >= TR::SMINL || r.count >= TR::SMINS + pen)) return 0;
+    return pack1 ? 1 : 2;
+  }
+  const uint32_t rng = r.p - iL + 1u;
+  sm = PK && r.sym == iY;
+  const bool shortOk = rng <= TR::MAXRANGE && (PK ? (sm || r.count >= TR::MEDIUM) : r.count >= TR::SHORT);   // (count >= 2 S >= the Packed SHORT of 3)
+  return shortOk ? 1 : (r.count >= TR::LONG ? 2 : 0);
 }
 
 template <int FAM, int S, int AL, int MODE>
@@ -70,7 +77,7 @@ __device__ __forceinline__ void ppS_block(const uint8_t *__restrict__ in, uint64
   constexpr bool LUT = FAM == LUT3;
   constexpr bool MTF3 = LUT || SH3;                                    // three-symbol move-to-front list, every run stored
   constexpr uint32_t SU = (uint32_t)S;
-  constexpr uint32_t SHORT = TR::SHORT, MEDIUM = TR::MEDIUM, LONG = TR::LONG, MAXR = TR::MAXRANGE;
+  constexpr uint32_t SHORT = TR::SHORT, LONG = TR::LONG;
   constexpr bool R7 = TR::kRange7;
   // bytes of the literal terminator's fixed part (plain / Packed: of either terminator's).  Short: 3 header bytes, u16 0, u32 literals + 2 and, without a list,
   // a zero symbol; the end terminator: 3 header bytes, u16 0, u16 0 and, without a list, one zero byte (rleX_Xsl_short.h:976-1032)
@@ -150,25 +157,21 @@ __device__ __forceinline__ void ppS_block(const uint8_t *__restrict__ in, uint64
     // candidates: the stretches of at least S bits (data over a small alphabet is full of shorter ones: d[j] == d[j + S] by accident -- with every stretch
     // a candidate the video-shaped rle64 buffer took 8 rounds per block).  full bit i: the S bits up to and including position i are all set
     // (log-step ANDs of the bits shifted up, the bits that come in from the lane in front taken from its top dword)
-    auto shl_in = [&](uint64_t v, uint32_t t) __attribute__((always_inline)) -> uint64_t {
-      const uint32_t top = wave_shr1((uint32_t)(v >> 32), 0u);
-      return (v << t) | (uint64_t)(top >> (32u - t));
-    };
     uint64_t full;
     {
-      const uint64_t c2 = m64 & shl_in(m64, 1u);
+      const uint64_t c2 = m64 & pp_shl_in(m64, 1u, 0u);
       if constexpr (S == 1) full = (TR::SMINS >= 3u) ? c2 : m64;            // (a run of two bytes can only be stored where the codec's shortest run is two)
       else if constexpr (S == 2) full = c2;
-      else if constexpr (S == 3) full = c2 & shl_in(m64, 2u);
+      else if constexpr (S == 3) full = c2 & pp_shl_in(m64, 2u, 0u);
       else
       {
-        const uint64_t c4 = c2 & shl_in(c2, 2u);
+        const uint64_t c4 = c2 & pp_shl_in(c2, 2u, 0u);
         if constexpr (S == 4) full = c4;
-        else if constexpr (S == 6) full = c4 & shl_in(c2, 4u);
-        else full = c4 & shl_in(c4, 4u);
+        else if constexpr (S == 6) full = c4 & pp_shl_in(c2, 4u, 0u);
+        else full = c4 & pp_shl_in(c4, 4u, 0u);
       }
     }
-    const uint64_t cands = ends & shl_in(full, 1u);                        // the stretch that ends in front of position i is full at i - 1
+    const uint64_t cands = ends & pp_shl_in(full, 1u, 0u);                        // the stretch that ends in front of position i is full at i - 1
     const uint32_t cnt = (uint32_t)__builtin_popcountll(cands);
     const uint32_t inclCnt = wave_scan_add(cnt);
     R = wave_lane(inclCnt, 63);
@@ -178,24 +181,6 @@ __device__ __forceinline__ void ppS_block(const uint8_t *__restrict__ in, uint64
     candAt = inclCnt - cnt;
   }
   wave_sync();
-
-  [[maybe_unused]] auto put_chunks = [&](uint32_t src, uint32_t ds, uint32_t len, uint32_t t0, uint32_t tStep, uint32_t tEnd) __attribute__((always_inline)) {
-    const uint32_t de = ds + len, D0 = ds & ~15u;
-    for (uint32_t t = t0; t < tEnd; t += tStep)
-    {
-      const uint32_t D = D0 + 16u * t;
-      const uint32_t wa = kPpInPad + src + D - ds;
-      const uint32_t *const wq = (const uint32_t *)(sh.inb + (wa & ~3u));
-      const uint32_t q0 = wq[0], q1 = wq[1], q2 = wq[2], q3 = wq[3], q4 = wq[4], sb = wa & 3u;
-      const u32x4 v = u32x4{ alignbyte(q1, q0, sb), alignbyte(q2, q1, sb), alignbyte(q3, q2, sb), alignbyte(q4, q3, sb) };
-      const uint32_t lo = D < ds ? ds - D : 0u, hi = de - D < 16u ? de - D : 16u;      // chunk bytes [lo, hi)
-      const u32x4 mh = lds_ld128(sh.mlut + (hi << 4)), ml = lds_ld128(sh.mlut + (lo << 4));
-      unsigned long long *const ip = (unsigned long long *)(sh.img + D);
-      const uint64_t w0 = (uint64_t)(v.x & mh.x & ~ml.x) | ((uint64_t)(v.y & mh.y & ~ml.y) << 32), w1 = (uint64_t)(v.z & mh.z & ~ml.z) | ((uint64_t)(v.w & mh.w & ~ml.w) << 32);
-      atomicOr(ip, w0);
-      atomicOr(ip + 1, w1);
-    }
-  };
 
   // ---- 2. one candidate (or record) per lane, 64 per round ----
   uint32_t carL = 0;                                 // lastRLE in front of the round's first candidate
@@ -227,7 +212,7 @@ __device__ __forceinline__ void ppS_block(const uint8_t *__restrict__ in, uint64
       inL = wave_shr1(outL, carL);
       if constexpr (SH3)
       {
-        // (one-byte or 3-byte header: from the gap and the count, as decide() below)
+        // (one-byte or 3-byte header: from the gap and the count, as ppS_decide())
         const uint32_t cnt = e - p, scu_ = AL ? cnt / SU - TR::SMINS / SU + 2u : cnt - TR::SMINS + 2u;
         if (have && !(p - inL <= TR::SMAXPR && scu_ - 2u <= TR::SMAXPC)) k = 2;
       }
@@ -256,26 +241,15 @@ __device__ __forceinline__ void ppS_block(const uint8_t *__restrict__ in, uint64
       bool geoKnown = !have || (lane != 0u ? s0 >= qLeft + SU : s0 >= carE);
       uint32_t outE = 0;                                                   // end of the last run up to and including this candidate
       bool outEKnown = false;
-      auto run_from = [&](uint32_t resume) __attribute__((always_inline)) {
-        // (p, e) of this stretch's run when the scan resumes at `resume`; e == 0: no run
-        const uint32_t ps = resume > s0 ? resume : s0;
-        p = ps; e = 0u;
-        if (have && q >= ps + SU)
-        {
-          const uint32_t Leff = q - ps;
-          const uint32_t whole = ((Leff + SU) / SU) * SU;
-          const uint32_t eW = ps + whole;
-          e = (!AL && eW + SU <= n) ? q + SU : eW;
-        }
-      };
-      if (geoKnown) { run_from(0u); outE = e; outEKnown = have && e != 0u; }   // (a candidate without a run hands its left neighbour's end through: not known yet)
+      const PpStretch stretch{ s0, p, e, have, q, n };
+      if (geoKnown) { pp_run_from<S, AL>(stretch, 0u); outE = e; outEKnown = have && e != 0u; }   // (a candidate without a run hands its left neighbour's end through: not known yet)
       if (!have) { outEKnown = true; outE = 0u; }
       for (uint32_t pass = 0; pass < 66u; pass++)
       {
         const uint32_t lk = wave_shr1(outEKnown ? 1u : 0u, 1u), le = wave_shr1(outE, carE);
         if (have && !outEKnown && lk != 0u)
         {
-          if (!geoKnown) { run_from(le); geoKnown = true; }
+          if (!geoKnown) { pp_run_from<S, AL>(stretch, le); geoKnown = true; }
           outE = (e != 0u) ? e : le;
           outEKnown = true;
         }
@@ -290,26 +264,7 @@ __device__ __forceinline__ void ppS_block(const uint8_t *__restrict__ in, uint64
       // (LUT, symbols of 3 bytes and more: EVERY run is stored -- count >= 2 S >= 6 >= 3 + the largest penalty a block can produce, rleX_Xsl.h:116-132 --
       //  so the chain below only hands lastRLE through the candidates without a run; what the list decides is the symbol's index, further down)
       const bool sure = isRun && (MTF3 || count >= (SH ? TR::SMINL : LONG));
-      auto decide = [&](uint32_t iL, uint64_t iY, bool &sm) __attribute__((always_inline)) -> int {
-        if constexpr (LUT) { sm = false; return 1; }
-        if constexpr (SH)
-        {
-          // process_symbol of the Short family (rleX_Xsl_short.h:152-215): the packet's size over the one-byte form is a penalty on the shortest run stored;
-          // 1: one-byte header, 2: the 3-byte form (with 16 bit fields behind it where count or range need them)
-          const uint32_t gp = p - iL, range = gp + 2u;
-          sm = SH1 && sym == iY;
-          const uint32_t scu = AL ? count / SU - TR::SMINS / SU + 2u : count - TR::SMINS + 2u;
-          const bool pack1 = gp <= TR::SMAXPR && scu - 2u <= TR::SMAXPC;
-          uint32_t pen = (SH1 && !sm) ? SU : 0u;
-          if (!pack1) pen += 2u + (range <= TR::SMAXTR ? 0u : 2u) + (scu <= TR::SMAXTC ? 0u : 2u);      // (nothing in a block needs a 32 bit field, nor the 20 bit penalty term: hsrle_codecs.h asserts the bound beside kPpwListMaxBlock)
-          if (!SH3 && !(count >= TR::SMINL || count >= TR::SMINS + pen)) return 0;
-          return pack1 ? 1 : 2;
-        }
-        const uint32_t rng = p - iL + 1u;
-        sm = PK && sym == iY;
-        const bool shortOk = rng <= MAXR && (PK ? (sm || count >= MEDIUM) : count >= SHORT);   // (count >= 2 S >= the Packed SHORT of 3)
-        return shortOk ? 1 : (count >= LONG ? 2 : 0);
-      };
+      const PpSRun run{ p, sym, count };
       uint64_t outY = sym, inY = 0;
       outL = e;
       bool outKnown = sure || !have, inKnown = !have;
@@ -322,12 +277,12 @@ __device__ __forceinline__ void ppS_block(const uint8_t *__restrict__ in, uint64
         if (inKnown && !outKnown)
         {
           bool sm;
-          if (!isRun || decide(inL, inY, sm) == 0) { outL = inL; outY = inY; }
+          if (!isRun || ppS_decide<FAM, S, AL, false>(run, inL, inY, sm) == 0) { outL = inL; outY = inY; }
           outKnown = true;
         }
         if (__ballot(!inKnown) == 0ull) break;
       }
-      k = isRun ? decide(inL, inY, same) : 0;
+      k = isRun ? ppS_decide<FAM, S, AL, false>(run, inL, inY, same) : 0;
       carY = (uint64_t)wave_lane((uint32_t)outY, lastLane) | ((uint64_t)wave_lane((uint32_t)(outY >> 32), lastLane) << 32);
       if constexpr (MTF3)
       {
@@ -437,8 +392,8 @@ __device__ __forceinline__ void ppS_block(const uint8_t *__restrict__ in, uint64
       }
       for (uint32_t t = 0; __ballot(t < nch) != 0ull; t += 2u)
       {
-        if (t < nch) put_chunks(inL, ds, gap, t, 1u, t + 1u);
-        if (t + 1u < nch) put_chunks(inL, ds, gap, t + 1u, 1u, t + 2u);
+        if (t < nch) pp_put_chunks(sh, inL, ds, gap, t, 1u, t + 1u);
+        if (t + 1u < nch) pp_put_chunks(sh, inL, ds, gap, t + 1u, 1u, t + 2u);
       }
     }
     carL = wave_lane(outL, lastLane);
@@ -495,7 +450,7 @@ __device__ __forceinline__ void ppS_block(const uint8_t *__restrict__ in, uint64
         uint32_t src, ds, len;
         if (j < nj) { const uint64_t jb = sh.jobs[j]; src = (uint32_t)jb & 0x1FFFu; ds = (uint32_t)(jb >> 13) & 0x1FFFu; len = (uint32_t)(jb >> 26); }
         else { src = carL; ds = pos + TERM; len = kLit; }
-        if (len != 0u) put_chunks(src, ds, len, lane, 64u, ((ds + len - 1u) >> 4) - (ds >> 4) + 1u);
+        if (len != 0u) pp_put_chunks(sh, src, ds, len, lane, 64u, ((ds + len - 1u) >> 4) - (ds >> 4) + 1u);
       }
     }
     wave_sync();
@@ -514,14 +469,7 @@ __global__ __launch_bounds__(64) void k_encodeS_pp(const uint8_t *__restrict__ i
                                                    const uint64_t *__restrict__ offsets, uint8_t *__restrict__ payload, PpScratch sc)
 {
   __shared__ PpShared<MODE != 0, true, FAM == LUT3 || FAM == SHORT3> sh;
-  if (MODE != 0 && threadIdx.x < 17u)
-  {
-    const uint32_t c = threadIdx.x;
-    const uint64_t part = ~(~0ull << (8u * (c & 7u)));
-    const bool hiHalf = c >= 8u;
-    const uint32_t p0 = (c == 16u) ? ~0u : (uint32_t)part, p1 = (c == 16u) ? ~0u : (uint32_t)(part >> 32);
-    lds_st128(sh.mlut + c * 16u, u32x4{ hiHalf ? ~0u : p0, hiHalf ? ~0u : p1, hiHalf ? p0 : 0u, hiHalf ? p1 : 0u });
-  }
+  if (MODE != 0) pp_init_mlut(sh.mlut);
   wave_sync();
   const uint32_t b = xcd_tile(blockIdx.x, gridDim.x);
   if (b < nBlocks)

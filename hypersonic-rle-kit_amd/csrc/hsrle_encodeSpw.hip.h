@@ -18,7 +18,6 @@
 #pragma once
 
 #include "hsrle_encodeSp.hip.h"
-#include "hsrle_encode8pw.hip.h"   // ppw_load, ppw_img16
 
 namespace hsrle {
 
@@ -45,7 +44,7 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
   constexpr bool LUT = FAM == LUT3;
   constexpr bool MTF3 = LUT || SH3;
   constexpr uint32_t SU = (uint32_t)S;
-  constexpr uint32_t SHORT = TR::SHORT, MEDIUM = TR::MEDIUM, LONG = TR::LONG, MAXR = TR::MAXRANGE;
+  constexpr uint32_t SHORT = TR::SHORT, LONG = TR::LONG;
   constexpr bool R7 = TR::kRange7;
   constexpr uint32_t TERM = SH ? ((SH1 || SH3) ? 9u : 9u + SU) : (LUT ? 8u : (PK ? 5u : SU + 5u) + (R7 ? 4u : 5u));
   constexpr uint32_t TERM_END = SH ? ((SH1 || SH3) ? 7u : 8u) : (LUT ? 6u : TERM);
@@ -90,13 +89,6 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
   for (uint32_t j = 0; j < 4u; j++) lds_st128(sh.inb + kPpInPad + base + 16u * j, x[j]);
   if (lane == 0u) lds_st128(sh.inb, front);
   if (lane == 63u) { lds_st128(sh.inb + kPpInPad + kPpMaxBlock, back0); lds_st128(sh.inb + kPpInPad + kPpMaxBlock + 16u, zero4); }
-
-  // the S-byte symbol of the run that starts at p (absolute) and reaches into this window
-  auto symbol_at = [&](uint32_t p) __attribute__((always_inline)) -> uint64_t {
-    uint32_t a = p;
-    if (ws >= 16u && p < ws - 16u) a = p + ((ws - 16u - p + SU - 1u) / SU) * SU;      // (a later period of the run: its pattern repeats every S bytes)
-    return pp_symbol<S>(sh.inb, kPpInPad + a - ws);
-  };
 
   // ---- 1. 64 match bits per lane: m[j] = (d[j] == d[j + S]) ----
   uint32_t R = recN;
@@ -156,22 +148,18 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
     const int32_t ownStart = (starts != 0ull) ? (int32_t)(base + 63u - (uint32_t)__builtin_clzll(starts)) : -1;
     const int32_t inclStart = wave_scan_max(ownStart);
     const uint32_t carryStart = wave_shr1((uint32_t)inclStart, 0xFFFFFFFFu);
-    auto shl_in = [&](uint64_t v, uint32_t t, uint32_t hist) __attribute__((always_inline)) -> uint64_t {
-      const uint32_t top = wave_shr1((uint32_t)(v >> 32), hist);
-      return (v << t) | (uint64_t)(top >> (32u - t));
-    };
     uint64_t full;
     {
-      const uint64_t c2 = m64 & shl_in(m64, 1u, histM);
+      const uint64_t c2 = m64 & pp_shl_in(m64, 1u, histM);
       if constexpr (S == 1) full = (TR::SMINS >= 3u) ? c2 : m64;
       else if constexpr (S == 2) full = c2;
-      else if constexpr (S == 3) full = c2 & shl_in(m64, 2u, histM);
+      else if constexpr (S == 3) full = c2 & pp_shl_in(m64, 2u, histM);
       else
       {
-        const uint64_t c4 = c2 & shl_in(c2, 2u, histC2);
+        const uint64_t c4 = c2 & pp_shl_in(c2, 2u, histC2);
         if constexpr (S == 4) full = c4;
-        else if constexpr (S == 6) full = c4 & shl_in(c2, 4u, histC2);
-        else full = c4 & shl_in(c4, 4u, histC4);
+        else if constexpr (S == 6) full = c4 & pp_shl_in(c2, 4u, histC2);
+        else full = c4 & pp_shl_in(c4, 4u, histC4);
       }
     }
     // (full of the position in front of the window, for the candidate at the window's first position)
@@ -182,7 +170,7 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
     else if constexpr (S == 4) histFull = histC4;
     else if constexpr (S == 6) histFull = histC4 & (histC2 << 4);
     else histFull = histC4 & (histC4 << 4);
-    uint64_t cands = ends & shl_in(full, 1u, histFull);
+    uint64_t cands = ends & pp_shl_in(full, 1u, histFull);
     if constexpr (MONO)
     {
       // a chunk's runs: those whose match stretch ends in it (its boundary run's does, at n - S .. n - 1; the next stretch of S set bits cannot end before n)
@@ -204,24 +192,6 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
     }
   }
   wave_sync();
-
-  [[maybe_unused]] auto put_chunks = [&](uint32_t src, uint32_t ds, uint32_t len, uint32_t t0, uint32_t tStep, uint32_t tEnd) __attribute__((always_inline)) {
-    const uint32_t de = ds + len, D0 = ds & ~15u;
-    for (uint32_t t = t0; t < tEnd; t += tStep)
-    {
-      const uint32_t D = D0 + 16u * t;
-      const uint32_t wa = kPpInPad + src + D - ds;
-      const uint32_t *const wq = (const uint32_t *)(sh.inb + (wa & ~3u));
-      const uint32_t q0 = wq[0], q1 = wq[1], q2 = wq[2], q3 = wq[3], q4 = wq[4], sb = wa & 3u;
-      const u32x4 v = u32x4{ alignbyte(q1, q0, sb), alignbyte(q2, q1, sb), alignbyte(q3, q2, sb), alignbyte(q4, q3, sb) };
-      const uint32_t lo = D < ds ? ds - D : 0u, hi = de - D < 16u ? de - D : 16u;
-      const u32x4 mh = lds_ld128(sh.mlut + (hi << 4)), ml = lds_ld128(sh.mlut + (lo << 4));
-      unsigned long long *const ip = (unsigned long long *)(sh.img + D);
-      const uint64_t w0 = (uint64_t)(v.x & mh.x & ~ml.x) | ((uint64_t)(v.y & mh.y & ~ml.y) << 32), w1 = (uint64_t)(v.z & mh.z & ~ml.z) | ((uint64_t)(v.w & mh.w & ~ml.w) << 32);
-      atomicOr(ip, w0);
-      atomicOr(ip + 1, w1);
-    }
-  };
 
   // ---- 2. one candidate (or record) per lane, 64 per round ----
   uint32_t carL = cs.carL, carE = cs.carE;
@@ -258,7 +228,7 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
         const uint32_t cnt = e - p, scu_ = AL ? cnt / SU - TR::SMINS / SU + 2u : cnt - TR::SMINS + 2u;
         if (have && !(p - inL <= TR::SMAXPR && scu_ - 2u <= TR::SMAXPC)) k = 2;
       }
-      sym = symbol_at(have ? p : ws);
+      sym = ppw_symbol_at<S>(sh, ws, have ? p : ws);
     }
     else
     {
@@ -287,25 +257,15 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
       bool geoKnown = !have || (lane != 0u ? s0 >= qLeft + SU : s0 >= carE);
       uint32_t outE = 0;
       bool outEKnown = false;
-      auto run_from = [&](uint32_t resume) __attribute__((always_inline)) {
-        const uint32_t ps = resume > s0 ? resume : s0;
-        p = ps; e = 0u;
-        if (have && q >= ps + SU)
-        {
-          const uint32_t Leff = q - ps;
-          const uint32_t whole = ((Leff + SU) / SU) * SU;
-          const uint32_t eW = ps + whole;
-          e = (!AL && eW + SU <= nE) ? q + SU : eW;
-        }
-      };
-      if (geoKnown) { run_from(0u); outE = e; outEKnown = have && e != 0u; }
+      const PpStretch stretch{ s0, p, e, have, q, nE };
+      if (geoKnown) { pp_run_from<S, AL>(stretch, 0u); outE = e; outEKnown = have && e != 0u; }
       if (!have) { outEKnown = true; outE = 0u; }
       for (uint32_t pass = 0; pass < 66u; pass++)
       {
         const uint32_t lk = wave_shr1(outEKnown ? 1u : 0u, 1u), le = wave_shr1(outE, carE);
         if (have && !outEKnown && lk != 0u)
         {
-          if (!geoKnown) { run_from(le); geoKnown = true; }
+          if (!geoKnown) { pp_run_from<S, AL>(stretch, le); geoKnown = true; }
           outE = (e != 0u) ? e : le;
           outEKnown = true;
         }
@@ -314,28 +274,10 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
       carE = wave_lane(outE, lastLane);
       const bool isRun = have && e != 0u;
       const uint32_t count = e - p;
-      sym = symbol_at(isRun ? p : ws);
+      sym = ppw_symbol_at<S>(sh, ws, isRun ? p : ws);
 
       const bool sure = isRun && (MTF3 || count >= (SH ? TR::SMINL : LONG));
-      auto decide = [&](uint32_t iL, uint64_t iY, bool &sm) __attribute__((always_inline)) -> int {
-        if constexpr (LUT) { sm = false; return 1; }
-        if constexpr (SH)
-        {
-          const uint32_t gp = p - iL, range = gp + 2u;
-          sm = SH1 && sym == iY;
-          const uint32_t scu = AL ? count / SU - TR::SMINS / SU + 2u : count - TR::SMINS + 2u;
-          const bool pack1 = gp <= TR::SMAXPR && scu - 2u <= TR::SMAXPC;
-          uint32_t pen = (SH1 && !sm) ? SU : 0u;
-          // (rleX_Xsl_short.h:197: above 20 bits a field costs 4 -- a chunk of a monolithic stream has no length limit; blocks end below it, hsrle_codecs.h: kPpwListMaxBlock)
-          if (!pack1) pen += 2u + (range <= 0xFFFFFu ? (range <= TR::SMAXTR ? 0u : 2u) : 4u) + (scu <= 0xFFFFFu ? (scu <= TR::SMAXTC ? 0u : 2u) : 4u);
-          if (!SH3 && !(count >= TR::SMINL || count >= TR::SMINS + pen)) return 0;
-          return pack1 ? 1 : 2;
-        }
-        const uint32_t rng = p - iL + 1u;
-        sm = PK && sym == iY;
-        const bool shortOk = rng <= MAXR && (PK ? (sm || count >= MEDIUM) : count >= SHORT);
-        return shortOk ? 1 : (count >= LONG ? 2 : 0);
-      };
+      const PpSRun run{ p, sym, count };
       uint64_t outY = sym, inY = 0;
       outL = e;
       bool outKnown = sure || !have, inKnown = !have;
@@ -347,12 +289,12 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
         if (inKnown && !outKnown)
         {
           bool sm;
-          if (!isRun || decide(inL, inY, sm) == 0) { outL = inL; outY = inY; }
+          if (!isRun || ppS_decide<FAM, S, AL, true>(run, inL, inY, sm) == 0) { outL = inL; outY = inY; }
           outKnown = true;
         }
         if (__ballot(!inKnown) == 0ull) break;
       }
-      k = isRun ? decide(inL, inY, same) : 0;
+      k = isRun ? ppS_decide<FAM, S, AL, true>(run, inL, inY, same) : 0;
       carY = (uint64_t)wave_lane((uint32_t)outY, lastLane) | ((uint64_t)wave_lane((uint32_t)(outY >> 32), lastLane) << 32);
       if constexpr (MTF3)
       {
@@ -392,7 +334,7 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
     const uint32_t cMax = (PK || LUT) ? 127u : 255u;
     // (blocks above 64 KiB: counts and ranges beyond 16 bits exist -- the LUT / Short forms then say 0 in the packed field and a 32 bit field follows: rleX_Xsl.h:190-250,
     //  rleX_Xsl_short.h:216-357.  The reference's penalty steps again at 0xFFFFF: block mode cannot get there -- the host keeps these codecs to blocks of at most
-    //  kPpwListMaxBlock, hsrle_codecs.h asserts it -- but a chunk of a monolithic stream can, and the Short `decide` above has the term)
+    //  kPpwListMaxBlock, hsrle_codecs.h asserts it -- but a chunk of a monolithic stream can, and ppS_decide<.., WIDE = true> has the term)
     const uint32_t cBytes = LUT ? (cfield <= 127u ? 0u : (cfield <= 0xFFFFu ? 2u : 4u)) : (cfield <= cMax ? 1u : 5u);
     const uint32_t sBytes = MTF3 ? (mtf == 3u ? SU : 0u) : (((PK || SH1) && same) ? 0u : SU);
     const uint32_t rBytes = LUT ? (rng <= 127u ? 0u : (rng <= 0xFFFFu ? 2u : 4u)) : ((k == 1) ? 1u : (R7 ? 4u : 5u));
@@ -478,8 +420,8 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
       }
       for (uint32_t t = 0; __ballot(t < nch) != 0ull; t += 2u)
       {
-        if (t < nch) put_chunks(inLw - ws, ds, gapImg, t, 1u, t + 1u);
-        if (t + 1u < nch) put_chunks(inLw - ws, ds, gapImg, t + 1u, 1u, t + 2u);
+        if (t < nch) pp_put_chunks(sh, inLw - ws, ds, gapImg, t, 1u, t + 1u);
+        if (t + 1u < nch) pp_put_chunks(sh, inLw - ws, ds, gapImg, t + 1u, 1u, t + 2u);
       }
       imgPos += wave_lane(incl, 63);
     }
@@ -550,7 +492,7 @@ __device__ __forceinline__ void ppSw_window(const uint8_t *__restrict__ d, uint3
         uint32_t src, ds, len;
         if (j < nj) { const uint64_t jb = sh.jobs[j]; src = (uint32_t)jb & 0x1FFFu; ds = (uint32_t)(jb >> 13) & 0x1FFFu; len = (uint32_t)(jb >> 26); }
         else { src = tailSrc; ds = imgPos + TERM; len = tailLen; }
-        if (len != 0u) put_chunks(src, ds, len, lane, 64u, ((ds + len - 1u) >> 4) - (ds >> 4) + 1u);
+        if (len != 0u) pp_put_chunks(sh, src, ds, len, lane, 64u, ((ds + len - 1u) >> 4) - (ds >> 4) + 1u);
       }
     }
     wave_sync();
@@ -667,14 +609,7 @@ template <int FAM, int S, int AL, bool MONO = false>
 __global__ __launch_bounds__(64) void k_encodeS_ppw_emit(PpwArgs a)
 {
   __shared__ PpShared<true, true, FAM == LUT3 || FAM == SHORT3> sh;
-  if (threadIdx.x < 17u)
-  {
-    const uint32_t c = threadIdx.x;
-    const uint64_t part = ~(~0ull << (8u * (c & 7u)));
-    const bool hiHalf = c >= 8u;
-    const uint32_t p0 = (c == 16u) ? ~0u : (uint32_t)part, p1 = (c == 16u) ? ~0u : (uint32_t)(part >> 32);
-    lds_st128(sh.mlut + c * 16u, u32x4{ hiHalf ? ~0u : p0, hiHalf ? ~0u : p1, hiHalf ? p0 : 0u, hiHalf ? p1 : 0u });
-  }
+  pp_init_mlut(sh.mlut);
   const uint32_t gw = xcd_tile(blockIdx.x, gridDim.x);
   if (gw >= a.nWindows) return;
   const uint32_t *const st = a.states + (uint64_t)gw * kPpwSStateWords;
