@@ -588,7 +588,7 @@ int hsrle_decompress_mono_dev(int codec, const void *dStream, uint32_t streamSiz
   if (hipMemcpyAsync(h16, dStream, streamSize < 16u ? streamSize : 16u, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess || hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
     return HSRLE_ERR_DEVICE;
   MonoHeader mh;
-  if (!mono_header(codec, h16, streamSize, outCapacity > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)outCapacity, &mh))
+  if (!mono_header(codec, h16, streamSize, clamp32(outCapacity), &mh))
     return HSRLE_ERR_FORMAT;
   const MonoPlan m = plan_mono(mh.codec, mh.U, mh.C, mh.p0);
   if (workspaceSize < m.total) return HSRLE_ERR_CAPACITY;
@@ -606,7 +606,7 @@ int hsrle_decompress_mono_dev_async(int codec, const void *dStream, const uint8_
   mono_align_workspace(dWorkspace, workspaceSize);
   if (!device_ok()) return HSRLE_ERR_DEVICE;
   MonoHeader mh;
-  if (!mono_header(codec, pHeader16, streamSize, outCapacity > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)outCapacity, &mh))
+  if (!mono_header(codec, pHeader16, streamSize, clamp32(outCapacity), &mh))
     return HSRLE_ERR_FORMAT;
   const MonoPlan m = plan_mono(mh.codec, mh.U, mh.C, mh.p0);
   if (workspaceSize < m.total) return HSRLE_ERR_CAPACITY;

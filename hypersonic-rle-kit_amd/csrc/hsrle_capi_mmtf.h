@@ -1,7 +1,8 @@
 // hsrle_capi_mmtf.h -- part of hsrle_capi.hip: C ABI of the mmtf / bitmmtf transforms (include/hsrle.h section 5; reference: src/rle.h:420-438, src/mmtf.c, src/bit_mmtf.c).
 // The plan (segment length, chunk length, workspace layout) is made here on the host from the size alone; inst_mmtf.hip launches it.
 // Behind it: the C ABI of the rle8_mmtf128 codec (reference: src/rle8_mmtf.c, src/rle.h:442-452), which runs the mmtf128 plan between its own passes
-// (kernels: hsrle_rle8mmtf.hip.h, launched by inst_rle8mmtf.hip).  No kernel here.  The host-pointer functions stage like every other family: one Staging.
+// (kernels: hsrle_rle8mmtf.hip.h, launched by inst_rle8mmtf.hip).  No kernel here.  The host-pointer functions take the staged trip of hsrle_capi_host.h;
+// rle8_mmtf128's device entries and host-pointer functions are the single-stream codecs' shared ones (hsrle_capi_host.h).
 #pragma once
 #include "hsrle_capi_host.h"
 #include "hsrle_mmtf.h"
@@ -84,11 +85,11 @@ static bool mmtf_plan(int transform, uint64_t size, MmtfPlan &p)
   if (p.chunks == 0u) p.chunks = 1u;
   if (chunkBound == 0u) chunkBound = 1u;
   p.offVals = 0;
-  p.total = 256u + ((4u * chunkBound + 255u) & ~255ull);
+  p.total = 256u + align_up(4u * chunkBound, 256);
   return true;
 }
 
-// ---- the host-pointer functions: one Staging each (hsrle_capi_host.h), so they run one after the other with every other drop-in call on the device ----
+// ---- the host-pointer functions: the staged trip (hsrle_capi_host.h), so they run one after the other with every other drop-in call on the device ----
 static uint32_t mmtf_dropin(int transform, int decode, const uint8_t *pIn, uint32_t inSize, uint8_t *pOut, uint32_t outSize)
 {
   if (pIn == nullptr || pOut == nullptr || inSize == 0u || inSize > outSize)   // (mmtf.c does not look at the pointers; a NULL here is a 0, not a fault)
@@ -96,19 +97,16 @@ static uint32_t mmtf_dropin(int transform, int decode, const uint8_t *pIn, uint3
   const uint64_t need = hsrle_mmtf_workspace_size(transform, inSize);
   if (need == 0u || !device_ok())
     return 0;
-  Staging s;
-  if (!s.reserve(inSize, inSize) || !s.reserve_ws(need) || !s.up(pIn, inSize))
-    return 0;
-  if (hsrle_mmtf_dev_async(transform, decode, s.in, inSize, s.out, s.ws, s.wsSize, nullptr) != HSRLE_OK || !s.down(pOut, s.out, inSize))   // (the copy synchronises the null stream)
-    return 0;
-  return inSize;
+  uint64_t size = 0;
+  const int rc = staged_call(
+    pIn, inSize, inSize, need, pOut, 0u, [&](Staging &s) { return hsrle_mmtf_dev_async(transform, decode, s.in, inSize, s.out, s.ws, s.wsSize, nullptr); },
+    [&](const uint32_t *, uint64_t &n) { n = inSize; return (int)HSRLE_OK; }, &size);
+  return rc == HSRLE_OK ? inSize : 0u;
 }
 
 // ---- rle8_mmtf128 (reference: src/rle8_mmtf.c): the mmtf128 plan above between the codec's own passes ----
 static std::atomic<uint32_t> g_rle8MmtfSpanRows{ 0 };
 constexpr uint32_t kRle8MmtfMaxIn = 1u << 30;
-
-static inline uint64_t up256(uint64_t v) { return (v + 255u) & ~255ull; }
 
 static bool rle8mmtf_plan(int decode, uint64_t size, Rle8MmtfPlan &p)
 {
@@ -121,56 +119,20 @@ static bool rle8mmtf_plan(int decode, uint64_t size, Rle8MmtfPlan &p)
   p.spans = (p.rows + p.SP - 1u) / p.SP;
   p.maxRec = p.rows + 1u;   // a record per non-null packet, and such a packet holds a row
   p.offRanks = 256u;
-  p.offA = p.offRanks + up256((uint64_t)p.size + 16u);
-  p.offB = p.offA + up256(16ull * (decode ? p.maxRec : p.spans));
-  p.offMmtf = p.offB + up256(decode ? 0u : 16ull * p.spans);
+  p.offA = p.offRanks + align_up((uint64_t)p.size + 16u, 256);
+  p.offB = p.offA + align_up(16ull * (decode ? p.maxRec : p.spans), 256);
+  p.offMmtf = p.offB + align_up(decode ? 0u : 16ull * p.spans, 256);
   p.total = 256u + p.offMmtf + p.mmtf.total;
   return true;
 }
 
 static uint32_t rle8mmtf_bounds(uint32_t inSize) { return inSize > kRle8MmtfMaxIn ? 0u : inSize + 8u; }   // rle8_mmtf.c:26-32
 
-// (size and status word of a host-pointer call: Staging::status)
-static uint32_t rle8mmtf_compress_dropin(const uint8_t *pIn, uint32_t inSize, uint8_t *pOut, uint32_t outSize)
-{
-  if (pIn == nullptr || pOut == nullptr || inSize == 0u || inSize > kRle8MmtfMaxIn || outSize < rle8mmtf_bounds(inSize))
-    return 0;
-  const uint64_t need = hsrle_rle8_mmtf128_workspace_size(0, inSize);
-  if (need == 0u || !device_ok())
-    return 0;
-  Staging s;
-  if (!s.reserve(inSize, inSize) || !s.reserve_ws(need) || !s.up(pIn, inSize))
-    return 0;
-  if (hsrle_rle8_mmtf128_compress_dev_async(s.in, inSize, s.out, (uint64_t)inSize + 64u, s.status, s.status + 1, s.ws, s.wsSize, nullptr) != HSRLE_OK)
-    return 0;
-  uint32_t h[2] = { 0u, 1u };   // size, status
-  if (!s.words(h, s.status, 2) || h[1] != HSRLE_RLE8_MMTF_DONE || h[0] == 0u || h[0] > outSize || !s.down(pOut, s.out, h[0]))
-    return 0;
-  return h[0];
-}
+static bool rle8mmtf_enc_plan(uint64_t size, Rle8MmtfPlan &p) { return rle8mmtf_plan(0, size, p); }
+static bool rle8mmtf_dec_plan(uint64_t size, Rle8MmtfPlan &p) { return rle8mmtf_plan(1, size, p); }
 
-static uint32_t rle8mmtf_decompress_dropin(const uint8_t *pIn, uint32_t inSize, uint8_t *pOut, uint32_t outSize)
-{
-  if (pIn == nullptr || pOut == nullptr || inSize < 8u || outSize == 0u)
-    return 0;
-  uint32_t hdr[2];
-  memcpy(hdr, pIn, 8);
-  const uint32_t expectedOut = hdr[0], expectedIn = hdr[1];
-  if (expectedOut > outSize || expectedIn > inSize || expectedOut == 0u || expectedOut > kRle8MmtfMaxIn || expectedIn < 8u)
-    return 0;
-  const uint64_t need = hsrle_rle8_mmtf128_workspace_size(1, expectedOut);
-  if (need == 0u || !device_ok())
-    return 0;
-  Staging s;
-  if (!s.reserve(expectedIn, expectedOut) || !s.reserve_ws(need) || !s.up(pIn, expectedIn))
-    return 0;
-  if (hsrle_rle8_mmtf128_decompress_dev_async(s.in, expectedIn, s.out, expectedOut, s.status, s.ws, s.wsSize, nullptr) != HSRLE_OK)
-    return 0;
-  uint32_t status = 1u;
-  if (!s.words(&status, s.status, 1) || status != HSRLE_RLE8_MMTF_DONE || !s.down(pOut, s.out, expectedOut))
-    return 0;
-  return expectedOut;
-}
+static const StreamCodec kRle8MmtfCodec = { hsrle_rle8_mmtf128_workspace_size, hsrle_rle8_mmtf128_compress_dev_async, hsrle_rle8_mmtf128_decompress_dev_async, kRle8MmtfMaxIn, 8u,
+                                            HSRLE_RLE8_MMTF_DONE };
 
 }   // namespace hsrle
 
@@ -187,39 +149,22 @@ uint64_t hsrle_rle8_mmtf128_workspace_size(int decode, uint64_t size)
 int hsrle_rle8_mmtf128_compress_dev_async(const void *dIn, uint64_t inSize, void *dOut, uint64_t outCapacity, uint32_t *dOutSize, uint32_t *dStatus, void *dWorkspace,
                                           uint64_t workspaceSize, void *stream)
 {
-  Rle8MmtfPlan p;
-  if (dIn == nullptr || dOut == nullptr || dOutSize == nullptr || dStatus == nullptr || dWorkspace == nullptr || !rle8mmtf_plan(false, inSize, p))
-    return HSRLE_ERR_ARGUMENT;
-  const uintptr_t a = (uintptr_t)dIn, b = (uintptr_t)dOut;
-  if ((a < b + outCapacity && b < a + inSize) || (((uintptr_t)dOutSize | (uintptr_t)dStatus) & 3u) != 0u)
-    return HSRLE_ERR_ARGUMENT;
-  if (outCapacity < inSize + 8u || workspaceSize < p.total)
-    return HSRLE_ERR_CAPACITY;
-  uint8_t *ws = (uint8_t *)(((uintptr_t)dWorkspace + 255u) & ~(uintptr_t)255u);
-  const uint32_t cap = outCapacity > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)outCapacity;
-  return rle8mmtf_compress_enqueue(p, (const uint8_t *)dIn, (uint8_t *)dOut, cap, dOutSize, dStatus, ws, (hipStream_t)stream) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
+  return stream_compress_entry<Rle8MmtfPlan>(rle8mmtf_enc_plan, rle8mmtf_compress_enqueue, dIn, inSize, dOut, outCapacity, dOutSize, dStatus, dWorkspace, workspaceSize, stream);
 }
 
 int hsrle_rle8_mmtf128_decompress_dev_async(const void *dStream, uint64_t streamSize, void *dOut, uint64_t outSize, uint32_t *dStatus, void *dWorkspace, uint64_t workspaceSize,
                                             void *stream)
 {
-  Rle8MmtfPlan p;
-  if (dStream == nullptr || dOut == nullptr || dStatus == nullptr || dWorkspace == nullptr || streamSize == 0u || !rle8mmtf_plan(true, outSize, p))
-    return HSRLE_ERR_ARGUMENT;
-  const uintptr_t a = (uintptr_t)dStream, b = (uintptr_t)dOut;
-  if ((a < b + outSize && b < a + streamSize) || ((uintptr_t)dStatus & 3u) != 0u)
-    return HSRLE_ERR_ARGUMENT;
-  if (workspaceSize < p.total)
-    return HSRLE_ERR_CAPACITY;
-  uint8_t *ws = (uint8_t *)(((uintptr_t)dWorkspace + 255u) & ~(uintptr_t)255u);
-  const uint32_t cap = streamSize > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)streamSize;
-  return rle8mmtf_decompress_enqueue(p, (const uint8_t *)dStream, cap, (uint8_t *)dOut, dStatus, ws, (hipStream_t)stream) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
+  return stream_decompress_entry<Rle8MmtfPlan>(rle8mmtf_dec_plan, rle8mmtf_decompress_enqueue, dStream, streamSize, dOut, outSize, dStatus, dWorkspace, workspaceSize, stream);
 }
 
 uint32_t rle8_mmtf128_compress_bounds(const uint32_t inSize) { return rle8mmtf_bounds(inSize); }
 uint32_t rle8_mmtf256_compress_bounds(const uint32_t inSize) { return rle8mmtf_bounds(inSize); }
-uint32_t rle8_mmtf128_compress(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize) { return rle8mmtf_compress_dropin(pIn, inSize, pOut, outSize); }
-uint32_t rle8_mmtf128_decompress(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize) { return rle8mmtf_decompress_dropin(pIn, inSize, pOut, outSize); }
+uint32_t rle8_mmtf128_compress(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize)
+{
+  return stream_compress_dropin(kRle8MmtfCodec, inSize, (uint64_t)inSize + 64u, pIn, inSize, pOut, outSize);
+}
+uint32_t rle8_mmtf128_decompress(const uint8_t *pIn, const uint32_t inSize, uint8_t *pOut, const uint32_t outSize) { return stream_decompress_dropin(kRle8MmtfCodec, pIn, inSize, pOut, outSize); }
 
 void hsrle_mmtf_tuning(uint32_t segmentRows) { g_mmtfSegmentRows.store(segmentRows); }
 
@@ -238,13 +183,11 @@ int hsrle_mmtf_dev_async(int transform, int decode, const void *dIn, uint64_t si
     return HSRLE_OK;
   if (dIn == nullptr || dOut == nullptr || dWorkspace == nullptr)
     return HSRLE_ERR_ARGUMENT;
-  const uintptr_t a = (uintptr_t)dIn, b = (uintptr_t)dOut;
-  if (a < b + size && b < a + size)
+  if (ranges_overlap(dIn, size, dOut, size))
     return HSRLE_ERR_ARGUMENT;
   if (workspaceSize < p.total)
     return HSRLE_ERR_CAPACITY;
-  uint8_t *ws = (uint8_t *)(((uintptr_t)dWorkspace + 255u) & ~(uintptr_t)255u);
-  return mmtf_enqueue(p, decode != 0, (const uint8_t *)dIn, (uint8_t *)dOut, ws, (hipStream_t)stream) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
+  return mmtf_enqueue(p, decode != 0, (const uint8_t *)dIn, (uint8_t *)dOut, workspace_start(dWorkspace), (hipStream_t)stream) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
 }
 
 uint32_t mmtf_bounds(const uint32_t inSize) { return inSize; }       // mmtf.c

@@ -1,6 +1,6 @@
 // hsrle_capi_shb.h -- part of hsrle_capi.hip: C ABI of the rle8_sh BLOCK CONTAINER (include/hsrle.h section 5): many independent rle8_sh streams per call.
 // The plan is made here on the host: one block's single-stream plans (hsrle_capi_sh.h) times the blocks in flight; inst_rle8shb.hip launches the groups
-// (kernels: hsrle_rle8shb.hip.h).  No kernel here.  The host-pointer functions stage through the one Staging.
+// (kernels: hsrle_rle8shb.hip.h).  No kernel here.  The host-pointer functions take the staged trip of hsrle_capi_host.h.
 #pragma once
 #include "hsrle_capi_sh.h"
 
@@ -75,12 +75,6 @@ static bool shb_info_consistent(const hsrle_rle8_sh_blocks_info_t &i)
          i.payloadSize <= i.totalSize && i.totalSize == shb_table_end(i.blockCount) + i.payloadSize + kShbPadBytes;
 }
 
-static inline bool shb_overlap(const void *p, uint64_t pn, const void *q, uint64_t qn)
-{
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + qn && b < a + pn;
-}
-
 }   // namespace hsrle
 
 extern "C" {
@@ -122,12 +116,13 @@ int hsrle_rle8_sh_compress_blocks_dev_async(const void *dIn, uint64_t inSize, ui
   if (dIn == nullptr || dOut == nullptr || dOutSize == nullptr || dStatus == nullptr || dWorkspace == nullptr || inSize == 0u || !shb_valid_block(B) ||
       !rle8shb_plan(inSize, B, shb_block_count(inSize, B), p))
     return HSRLE_ERR_ARGUMENT;
-  if (shb_overlap(dIn, inSize, dOut, outCapacity) || ((uintptr_t)dOutSize & 7u) != 0u || ((uintptr_t)dStatus & 3u) != 0u)
+  if (ranges_overlap(dIn, inSize, dOut, outCapacity) || !word_aligned(dOutSize, 8) || !word_aligned(dStatus, 4))
     return HSRLE_ERR_ARGUMENT;
   if (outCapacity < shb_table_end(p.blockCount) + kShbPadBytes || workspaceSize < 512u + (uint64_t)p.inFlight * p.enc.total)
     return HSRLE_ERR_CAPACITY;
-  uint8_t *ws = (uint8_t *)(((uintptr_t)dWorkspace + 255u) & ~(uintptr_t)255u);
-  return rle8shb_compress_enqueue(p, (const uint8_t *)dIn, (uint8_t *)dOut, outCapacity, dOutSize, dStatus, ws, (hipStream_t)stream) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
+  return rle8shb_compress_enqueue(p, (const uint8_t *)dIn, (uint8_t *)dOut, outCapacity, dOutSize, dStatus, workspace_start(dWorkspace), (hipStream_t)stream) == hipSuccess
+           ? HSRLE_OK
+           : HSRLE_ERR_DEVICE;
 }
 
 int hsrle_rle8_sh_decompress_blocks_dev_async(const void *dContainer, const hsrle_rle8_sh_blocks_info_t *info, uint32_t firstBlock, uint32_t blockCount, void *dOut,
@@ -140,12 +135,12 @@ int hsrle_rle8_sh_decompress_blocks_dev_async(const void *dContainer, const hsrl
     return HSRLE_ERR_ARGUMENT;
   if (outCapacity < info->uncompressedSize)
     return HSRLE_ERR_CAPACITY;
-  if (shb_overlap(dContainer, info->totalSize, dOut, info->uncompressedSize) || ((uintptr_t)dStatus & 3u) != 0u)
+  if (ranges_overlap(dContainer, info->totalSize, dOut, info->uncompressedSize) || !word_aligned(dStatus, 4))
     return HSRLE_ERR_ARGUMENT;
   if (workspaceSize < 512u + (uint64_t)p.inFlight * p.dec.total)
     return HSRLE_ERR_CAPACITY;
-  uint8_t *ws = (uint8_t *)(((uintptr_t)dWorkspace + 255u) & ~(uintptr_t)255u);
-  return rle8shb_decompress_enqueue(p, (const uint8_t *)dContainer, info->payloadSize, firstBlock, blockCount, (uint8_t *)dOut, dStatus, ws, (hipStream_t)stream) == hipSuccess
+  return rle8shb_decompress_enqueue(p, (const uint8_t *)dContainer, info->payloadSize, firstBlock, blockCount, (uint8_t *)dOut, dStatus, workspace_start(dWorkspace),
+                                    (hipStream_t)stream) == hipSuccess
            ? HSRLE_OK
            : HSRLE_ERR_DEVICE;
 }
@@ -156,20 +151,19 @@ int hsrle_rle8_sh_compress_blocks_host(const void *pIn, uint64_t inSize, uint32_
   const uint64_t bound = hsrle_rle8_sh_blocks_bound(inSize, blockSize), need = hsrle_rle8_sh_blocks_workspace_size(0, inSize, blockSize);
   if (bound == 0u || need == 0u) return HSRLE_ERR_ARGUMENT;
   if (!device_ok()) return HSRLE_ERR_DEVICE;
-  Staging s;
-  if (!s.reserve(inSize, bound) || !s.reserve_ws(need) || !s.up(pIn, inSize))
-    return HSRLE_ERR_DEVICE;
+  uint64_t total = 0;
   // (the status words are 64-byte aligned: the size word is their first 8 bytes, the status the word behind)
-  const int rc = hsrle_rle8_sh_compress_blocks_dev_async(s.in, inSize, blockSize, s.out, bound, (uint64_t *)s.status, s.status + 2, s.ws, s.wsSize, nullptr);
-  if (rc != HSRLE_OK) return rc;
-  uint32_t h[3] = { 0u, 0u, 1u };
-  if (!s.words(h, s.status, 3)) return HSRLE_ERR_DEVICE;
-  const uint64_t total = (uint64_t)h[0] | (uint64_t)h[1] << 32;
-  if (h[2] != HSRLE_RLE8_SH_DONE || total == 0u) return HSRLE_ERR_DEVICE;   // (the bound always suffices)
-  if (total > outCapacity) return HSRLE_ERR_CAPACITY;
-  if (!s.down(pOut, s.out, total)) return HSRLE_ERR_DEVICE;
-  if (pContainerSize) *pContainerSize = total;
-  return HSRLE_OK;
+  const int rc = staged_call(
+    pIn, inSize, bound, need, pOut, 3u,
+    [&](Staging &s) { return hsrle_rle8_sh_compress_blocks_dev_async(s.in, inSize, blockSize, s.out, bound, (uint64_t *)s.status, s.status + 2, s.ws, s.wsSize, nullptr); },
+    [&](const uint32_t *h, uint64_t &n) {
+      n = (uint64_t)h[0] | (uint64_t)h[1] << 32;
+      if (h[2] != HSRLE_RLE8_SH_DONE || n == 0u) return (int)HSRLE_ERR_DEVICE;   // (the bound always suffices)
+      return n > outCapacity ? (int)HSRLE_ERR_CAPACITY : (int)HSRLE_OK;
+    },
+    &total);
+  if (rc == HSRLE_OK && pContainerSize) *pContainerSize = total;
+  return rc;
 }
 
 int hsrle_rle8_sh_decompress_blocks_host(const void *pContainer, uint64_t containerSize, void *pOut, uint64_t outCapacity, uint64_t *pUncompressedSize)
@@ -181,17 +175,13 @@ int hsrle_rle8_sh_decompress_blocks_host(const void *pContainer, uint64_t contai
   const uint64_t need = hsrle_rle8_sh_blocks_workspace_size(1, info.uncompressedSize, info.blockSize);
   if (need == 0u) return HSRLE_ERR_ARGUMENT;
   if (!device_ok()) return HSRLE_ERR_DEVICE;
-  Staging s;
-  if (!s.reserve(info.totalSize, info.uncompressedSize) || !s.reserve_ws(need) || !s.up(pContainer, info.totalSize))
-    return HSRLE_ERR_DEVICE;
-  rc = hsrle_rle8_sh_decompress_blocks_dev_async(s.in, &info, 0u, info.blockCount, s.out, info.uncompressedSize, s.status, s.ws, s.wsSize, nullptr);
-  if (rc != HSRLE_OK) return rc;
-  uint32_t status = 1u;
-  if (!s.words(&status, s.status, 1)) return HSRLE_ERR_DEVICE;
-  if (status != HSRLE_RLE8_SH_DONE) return HSRLE_ERR_FORMAT;
-  if (!s.down(pOut, s.out, info.uncompressedSize)) return HSRLE_ERR_DEVICE;
-  if (pUncompressedSize) *pUncompressedSize = info.uncompressedSize;
-  return HSRLE_OK;
+  uint64_t size = 0;
+  rc = staged_call(
+    pContainer, info.totalSize, info.uncompressedSize, need, pOut, 1u,
+    [&](Staging &s) { return hsrle_rle8_sh_decompress_blocks_dev_async(s.in, &info, 0u, info.blockCount, s.out, info.uncompressedSize, s.status, s.ws, s.wsSize, nullptr); },
+    [&](const uint32_t *h, uint64_t &n) { n = info.uncompressedSize; return h[0] != HSRLE_RLE8_SH_DONE ? (int)HSRLE_ERR_FORMAT : (int)HSRLE_OK; }, &size);
+  if (rc == HSRLE_OK && pUncompressedSize) *pUncompressedSize = size;
+  return rc;
 }
 
 }   // extern "C"

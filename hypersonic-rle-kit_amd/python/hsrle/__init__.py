@@ -75,6 +75,168 @@ class MonoIndexInfo(ctypes.Structure):
     ]
 
 
+class Rle8mInfo(ctypes.Structure):
+    """hsrle_rle8m_info_t: the header fields of an rle8m stream."""
+
+    _fields_ = [("compressedSize", ctypes.c_uint32), ("uncompressedSize", ctypes.c_uint32), ("sections", ctypes.c_uint32)]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the signatures of include/hsrle.h as data: symbol -> (restype, argtypes).  tests/test_binding_signatures.py holds them against the header's prototypes:
+# a pointer to void or to an integer is c_void_p (POINTER of the integer where a caller passes byref of one), const char * is c_char_p, a pointer to one of
+# the four info structs is POINTER of its class above, every other struct pointer is c_void_p, scalars are themselves.
+
+
+def _signatures():
+    ci, u32, u64, vp, cs, P = ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER
+    kit, shb, idx, r8m = P(ContainerInfo), P(Rle8ShBlocksInfo), P(MonoIndexInfo), P(Rle8mInfo)
+    stream_enc, stream_dec = (ci, [vp, u64, vp, u64, vp, vp, vp, u64, vp]), (ci, [vp, u64, vp, u64, vp, vp, u64, vp])
+    table = {
+        "hsrle_codec_from_name": (ci, [cs]),
+        "hsrle_codec_name": (cs, [ci]),
+        "hsrle_status_string": (cs, [ci]),
+        "hsrle_version": (cs, []),
+        "hsrle_build_id": (cs, []),
+        "hsrle_device_count": (ci, []),
+        "hsrle_experiments_enabled": (ci, []),
+        "hsrle_scratch_retention": (ci, [u64]),
+        "hsrle_trim": (ci, []),
+        "hsrle_encode_path": (ci, [ci, u64, u32]),
+        "hsrle_decode_ring": (ci, [ci, u64, u64]),
+        "hsrle_suggest_block_size": (u32, [u64]),
+        "hsrle_kernel_waves_per_cu": (ci, [ci, ci]),
+        "rle_compress_bounds": (u32, [u32]),
+        "rle_decompress_additional_size": (u32, []),
+        # 1. monolithic streams: host pointers, device pointers, the persistent index
+        "hsrle_compress_mono": (u32, [ci, vp, u32, vp, u32]),
+        "hsrle_decompress_mono": (u32, [ci, vp, u32, vp, u32]),
+        "hsrle_decompress_mono_workspace_size": (u64, [ci, u32, u32]),
+        "hsrle_compress_mono_workspace_size": (u64, [ci, u32]),
+        "hsrle_decompress_mono_dev": (ci, [ci, vp, u32, vp, u64, vp, u64, P(u32), P(u32), vp]),
+        "hsrle_decompress_mono_dev_async": (ci, [ci, vp, vp, u32, vp, u64, vp, u64, P(u32), vp, vp]),
+        "hsrle_compress_mono_dev": (ci, [ci, vp, u32, vp, u64, vp, u64, P(u32), P(u32), vp]),
+        "hsrle_compress_mono_dev_async": (ci, [ci, vp, u32, vp, u64, vp, u64, vp, vp]),
+        "hsrle_compress_mono_dev_enqueue": (ci, [ci, vp, u32, vp, u64, vp, u64, vp, vp, vp]),
+        "hsrle_mono_tuning": (None, [u32, u32, u32]),
+        "hsrle_mono_encode_stats": (None, [P(u32)]),
+        "hsrle_mono_index_size": (u64, [ci, u32, u32, u32]),
+        "hsrle_mono_index_workspace_size": (u64, [ci, u32, u32, u32]),
+        "hsrle_mono_index_build_dev": (ci, [ci, vp, u32, u32, vp, u64, vp, u64, idx, vp]),
+        "hsrle_mono_index_info_host": (ci, [vp, u64, idx]),
+        "hsrle_mono_decompress_range_dev_async": (ci, [vp, vp, idx, u64, u64, vp, u64, vp, vp]),
+        # 2. the block container
+        "hsrle_container_bound": (u64, [u64, u32]),
+        "hsrle_compress_workspace_size": (u64, [u64, u32]),
+        "hsrle_compress_workspace_size_codec": (u64, [ci, u64, u32]),
+        "hsrle_compress_dev_async": (ci, [ci, vp, u64, vp, u64, u32, vp, u64, vp]),
+        "hsrle_compress_dev": (ci, [ci, vp, u64, vp, u64, u32, P(u64), vp]),
+        "hsrle_container_info_dev": (ci, [vp, u64, kit, vp]),
+        "hsrle_container_info_host": (ci, [vp, u64, kit]),
+        "hsrle_decompress_dev_async": (ci, [vp, kit, vp, u64, vp, vp]),
+        "hsrle_decompress_blocks_dev_async": (ci, [vp, kit, u32, u32, vp, u64, vp, vp]),
+        "hsrle_decompress_range_dev_async": (ci, [vp, kit, u64, u64, vp, u64, vp, vp]),
+        "hsrle_decompress_dev": (ci, [vp, u64, vp, u64, P(u64), vp]),
+        "hsrle_compress_host": (ci, [ci, vp, u64, vp, u64, u32, P(u64)]),
+        "hsrle_decompress_host": (ci, [vp, u64, vp, u64, P(u64)]),
+        "hsrle_split_sub_block_size": (u32, [kit, u32]),
+        "hsrle_decompress_split_workspace_size": (u64, [kit, u32, u32]),
+        "hsrle_decompress_split_dev_async": (ci, [vp, kit, u32, u32, vp, u64, vp, vp, u64, u32, vp]),
+        "hsrle_hash_blocks_dev_async": (ci, [vp, kit, u32, u32, vp, vp]),
+        "hsrle_synth_dev_async": (ci, [ci, ci, u64, vp, u64, vp]),
+        # 4. containers across ranks
+        "hsrle_rccl_unique_id": (ci, [vp]),
+        "hsrle_rccl_comm_create": (ci, [vp, ci, ci, P(vp)]),
+        "hsrle_rccl_comm_destroy": (ci, [vp]),
+        "hsrle_rccl_comm_ranks": (ci, [vp, P(ci), P(ci)]),
+        "hsrle_gather_container_rccl": (ci, [vp, ci, vp, u64, u64, vp, u64, P(u64), vp]),
+        "hsrle_scatter_container_rccl": (ci, [vp, ci, vp, u64, vp, u64, P(u64), vp]),
+        # rle8m and the low-entropy codec
+        "rle8m_opencl_init": (ctypes.c_bool, [ctypes.c_size_t] * 3),
+        "rle8m_opencl_destroy": (None, []),
+        "rle8m_compress_bounds": (u32, [u32, u32]),
+        "rle8m_compress": (u32, [u32, vp, u32, vp, u32]),
+        "rle8_low_entropy_compress_bounds": (u32, [u32]),
+        "rle8_low_entropy_short_compress_bounds": (u32, [u32]),
+        "rle8_low_entropy_decompressed_size": (u32, [vp, u32]),
+        "rle8_low_entropy_get_compress_info": (ctypes.c_bool, [vp, u32, vp]),
+        "rle8_low_entropy_get_compress_info_only_max_frequency": (ctypes.c_bool, [vp, u32, vp]),
+        "rle8_low_entropy_write_compress_info": (u32, [vp, vp, u32]),
+        "rle8_low_entropy_read_decompress_info": (u32, [vp, u32, vp]),
+        "rle8_low_entropy_compress_with_info": (u32, [vp, u32, vp, vp, u32]),
+        "rle8_low_entropy_short_compress_with_info": (u32, [vp, u32, vp, vp, u32]),
+        "rle8_low_entropy_decompress_with_info": (u32, [vp, vp, vp, vp, u32]),
+        "rle8_low_entropy_short_decompress_with_info": (u32, [vp, vp, vp, vp, u32]),
+        "hsrle_low_entropy_workspace_size": (u64, [u32]),
+        "hsrle_low_entropy_compress_dev_async": (ci, [vp, u32, ci, vp, u64, vp, u64, vp, vp]),
+        "hsrle_low_entropy_decompress_workspace_size": (u64, [u64]),
+        "hsrle_low_entropy_decompress_dev": (ci, [vp, u64, vp, u64, vp, u64, vp, vp]),
+        "hsrle_rle8m_compress_workspace_size": (u64, [u32, u32]),
+        "hsrle_rle8m_compress_dev_async": (ci, [vp, u32, u32, vp, u64, vp, u64, vp, vp]),
+        "hsrle_rle8m_info_dev": (ci, [vp, u64, r8m, vp]),
+        "hsrle_rle8m_decompress_dev_async": (ci, [vp, r8m, vp, u64, vp, vp]),
+        # 5. the stream codecs: the mmtf transforms, rle8_mmtf128, rle8_sh and its block container
+        "hsrle_mmtf_workspace_size": (u64, [ci, u64]),
+        "hsrle_mmtf_dev_async": (ci, [ci, ci, vp, u64, vp, vp, u64, vp]),
+        "hsrle_mmtf_tuning": (None, [u32]),
+        "hsrle_rle8_mmtf128_workspace_size": (u64, [ci, u64]),
+        "hsrle_rle8_mmtf128_compress_dev_async": stream_enc,
+        "hsrle_rle8_mmtf128_decompress_dev_async": stream_dec,
+        "hsrle_rle8_mmtf_tuning": (None, [u32]),
+        "hsrle_rle8_sh_workspace_size": (u64, [ci, u64]),
+        "hsrle_rle8_sh_capacity": (u64, [u64]),
+        "hsrle_rle8_sh_compress_dev_async": stream_enc,
+        "hsrle_rle8_sh_decompress_dev_async": stream_dec,
+        "hsrle_rle8_sh_tuning": (None, [u32, u32, u32]),
+        "hsrle_rle8_sh_blocks_bound": (u64, [u64, u32]),
+        "hsrle_rle8_sh_blocks_workspace_size": (u64, [ci, u64, u32]),
+        "hsrle_rle8_sh_blocks_info_host": (ci, [vp, u64, shb]),
+        "hsrle_rle8_sh_blocks_info_dev": (ci, [vp, u64, shb, vp]),
+        "hsrle_rle8_sh_compress_blocks_dev_async": (ci, [vp, u64, u32, vp, u64, vp, vp, vp, u64, vp]),
+        "hsrle_rle8_sh_decompress_blocks_dev_async": (ci, [vp, shb, u32, u32, vp, u64, vp, vp, u64, vp]),
+        "hsrle_rle8_sh_compress_blocks_host": (ci, [vp, u64, u32, vp, u64, P(u64)]),
+        "hsrle_rle8_sh_decompress_blocks_host": (ci, [vp, u64, vp, u64, P(u64)]),
+        "hsrle_rle8_sh_blocks_tuning": (None, [u32]),
+    }
+    for nm in ("mmtf_bounds", "bitmmtf_bounds", "rle8_mmtf128_compress_bounds", "rle8_mmtf256_compress_bounds", "rle8_sh_bounds"):
+        table[nm] = (u32, [u32])
+    # the rule of the reference-named host-pointer functions (src/rle.h): (pIn, inSize, pOut, outSize) -> size, 0 = failure
+    widths = (16, 24, 32, 48, 64)
+    pairs = ["rle8_3symlut", "rle8_7symlut", "rle8m", "rle8_low_entropy", "rle8_low_entropy_short", "rle8_mmtf128", "rle8_sh"]
+    pairs += [f"rle{W}_{v}" for W in widths + (128,) for v in ("sym", "sym_packed", "byte", "byte_packed")]
+    pairs += [f"rle{W}_{k}symlut_{v}" for W in widths for k in (3, 7) for v in ("sym", "byte")]
+    pairs += [f"rle8_{v}_short" for v in ("multi", "single", "1symlut", "3symlut", "7symlut")]
+    pairs += [f"rle{W}_{v}_short" for W in widths for v in ("sym", "byte")] + [f"rle{W}_{k}symlut_{v}_short" for W in widths for k in (1, 3, 7) for v in ("sym", "byte")]
+    names = [p + d for p in pairs for d in ("_compress", "_decompress")]
+    names += ["rle8_multi_compress", "rle8_single_compress", "rle8_decompress", "rle8_packed_multi_compress", "rle8_packed_single_compress", "rle8_packed_decompress"]
+    names += [f"rle{W}_{k}symlut_byte_short_compress_greedy" for W in widths for k in (1, 3, 7)]
+    names += [f"{t}_{d}" for t in ("mmtf128", "mmtf256", "bitmmtf8", "bitmmtf16") for d in ("encode", "decode")]
+    names += ["rle8_low_entropy_compress_only_max_frequency", "rle8_low_entropy_short_compress_only_max_frequency", "rle8m_opencl_decompress"]
+    names.remove("rle8m_compress")                                       # (its first argument is the section count: in the table above)
+    for nm in names:
+        table[nm] = (u32, [vp, u32, vp, u32])
+    return table
+
+
+SIGNATURES = _signatures()
+EXPERIMENT_SIGNATURES = {                                                # -DHSRLE_EXPERIMENTS builds only: declared where the library has them
+    "hsrle_decompress_wave_dev_async": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ContainerInfo), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
+                                                       ctypes.c_void_p, ctypes.c_void_p]),
+}
+
+
+def declare(L):
+    """Give every function of include/hsrle.h its restype / argtypes on the ctypes.CDLL `L` (any build of libhsrle_hip.so).  Needs nothing but ctypes:
+    no torch, no device.  A function without them would take ctypes' default of int and truncate a 64 bit size without a word."""
+    for name, (restype, argtypes) in SIGNATURES.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
+    for name, (restype, argtypes) in EXPERIMENT_SIGNATURES.items():
+        if hasattr(L, name):
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
+    return L
+
+
 _LIB = None
 
 
@@ -91,152 +253,8 @@ def _lib():
         pass
     if not os.path.exists(LIB_PATH):
         raise RuntimeError(f"{LIB_PATH} is missing: build it with `make -C {PKG_DIR}` (hipcc, gfx950); there is no fallback codec")
-    L = ctypes.CDLL(LIB_PATH)
-    u8p, u32, u64, vp, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int
-    L.hsrle_codec_from_name.restype = ci
-    L.hsrle_codec_from_name.argtypes = [ctypes.c_char_p]
-    L.hsrle_codec_name.restype = ctypes.c_char_p
-    L.hsrle_codec_name.argtypes = [ci]
-    L.hsrle_status_string.restype = ctypes.c_char_p
-    L.hsrle_status_string.argtypes = [ci]
-    L.hsrle_version.restype = ctypes.c_char_p
-    L.hsrle_device_count.restype = ci
-    L.hsrle_experiments_enabled.restype = ci
-    L.hsrle_encode_path.restype = ci
-    L.hsrle_encode_path.argtypes = [ci, ctypes.c_uint64, ctypes.c_uint32]
-    L.hsrle_decode_ring.restype = ci
-    L.hsrle_decode_ring.argtypes = [ci, ctypes.c_uint64, ctypes.c_uint64]
-    L.hsrle_build_id.restype = ctypes.c_char_p
-    L.hsrle_suggest_block_size.restype = u32
-    L.hsrle_suggest_block_size.argtypes = [u64]
-    L.hsrle_kernel_waves_per_cu.restype = ci
-    L.hsrle_kernel_waves_per_cu.argtypes = [ci, ci]
-    L.rle_compress_bounds.restype = u32
-    L.rle_compress_bounds.argtypes = [u32]
-    L.rle_decompress_additional_size.restype = u32
-    for nm in ("hsrle_compress_mono", "hsrle_decompress_mono"):
-        f = getattr(L, nm)
-        f.restype = u32
-        f.argtypes = [ci, u8p, u32, u8p, u32]
-    L.hsrle_container_bound.restype = u64
-    L.hsrle_container_bound.argtypes = [u64, u32]
-    L.hsrle_compress_workspace_size.restype = u64
-    L.hsrle_compress_workspace_size.argtypes = [u64, u32]
-    L.hsrle_compress_workspace_size_codec.restype = u64
-    L.hsrle_compress_workspace_size_codec.argtypes = [ctypes.c_int, u64, u32]
-    L.hsrle_compress_dev_async.restype = ci
-    L.hsrle_compress_dev_async.argtypes = [ci, vp, u64, vp, u64, u32, vp, u64, vp]
-    L.hsrle_compress_dev.restype = ci
-    L.hsrle_compress_dev.argtypes = [ci, vp, u64, vp, u64, u32, ctypes.POINTER(u64), vp]
-    L.hsrle_container_info_dev.restype = ci
-    L.hsrle_container_info_dev.argtypes = [vp, u64, ctypes.POINTER(ContainerInfo), vp]
-    L.hsrle_container_info_host.restype = ci
-    L.hsrle_container_info_host.argtypes = [vp, u64, ctypes.POINTER(ContainerInfo)]
-    L.hsrle_decompress_dev_async.restype = ci
-    L.hsrle_decompress_dev_async.argtypes = [vp, ctypes.POINTER(ContainerInfo), vp, u64, vp, vp]
-    L.hsrle_decompress_blocks_dev_async.restype = ci
-    L.hsrle_decompress_blocks_dev_async.argtypes = [vp, ctypes.POINTER(ContainerInfo), u32, u32, vp, u64, vp, vp]
-    L.hsrle_decompress_dev.restype = ci
-    L.hsrle_decompress_dev.argtypes = [vp, u64, vp, u64, ctypes.POINTER(u64), vp]
-    L.hsrle_compress_host.restype = ci
-    L.hsrle_compress_host.argtypes = [ci, vp, u64, vp, u64, u32, ctypes.POINTER(u64)]
-    L.hsrle_decompress_host.restype = ci
-    L.hsrle_decompress_host.argtypes = [vp, u64, vp, u64, ctypes.POINTER(u64)]
-    L.hsrle_decompress_mono_workspace_size.restype = u64
-    L.hsrle_decompress_mono_workspace_size.argtypes = [ci, u32, u32]
-    L.hsrle_decompress_mono_dev.restype = ci
-    L.hsrle_decompress_mono_dev.argtypes = [ci, vp, u32, vp, u64, vp, u64, ctypes.POINTER(u32), ctypes.POINTER(u32), vp]
-    L.hsrle_compress_mono_workspace_size.restype = u64
-    L.hsrle_compress_mono_workspace_size.argtypes = [ci, u32]
-    L.hsrle_decompress_mono_dev_async.restype = ci
-    L.hsrle_decompress_mono_dev_async.argtypes = [ci, vp, ctypes.c_char_p, u32, vp, u64, vp, u64, ctypes.POINTER(u32), vp, vp]
-    L.hsrle_compress_mono_dev.restype = ci
-    L.hsrle_compress_mono_dev.argtypes = [ci, vp, u32, vp, u64, vp, u64, ctypes.POINTER(u32), ctypes.POINTER(u32), vp]
-    L.hsrle_compress_mono_dev_async.restype = ci
-    L.hsrle_compress_mono_dev_async.argtypes = [ci, vp, u32, vp, u64, vp, u64, vp, vp]
-    L.hsrle_compress_mono_dev_enqueue.restype = ci
-    L.hsrle_compress_mono_dev_enqueue.argtypes = [ci, vp, u32, vp, u64, vp, u64, vp, vp, vp]
-    L.hsrle_mono_index_size.restype = u64
-    L.hsrle_mono_index_size.argtypes = [ci, u32, u32, u32]
-    L.hsrle_mono_index_workspace_size.restype = u64
-    L.hsrle_mono_index_workspace_size.argtypes = [ci, u32, u32, u32]
-    L.hsrle_mono_index_build_dev.restype = ci
-    L.hsrle_mono_index_build_dev.argtypes = [ci, vp, u32, u32, vp, u64, vp, u64, ctypes.POINTER(MonoIndexInfo), vp]
-    L.hsrle_mono_index_info_host.restype = ci
-    L.hsrle_mono_index_info_host.argtypes = [vp, u64, ctypes.POINTER(MonoIndexInfo)]
-    L.hsrle_mono_decompress_range_dev_async.restype = ci
-    L.hsrle_mono_decompress_range_dev_async.argtypes = [vp, vp, ctypes.POINTER(MonoIndexInfo), u64, u64, vp, u64, vp, vp]
-    L.hsrle_decompress_range_dev_async.restype = ci
-    L.hsrle_decompress_range_dev_async.argtypes = [vp, ctypes.POINTER(ContainerInfo), u64, u64, vp, u64, vp, vp]
-    L.hsrle_mono_tuning.restype = None
-    L.hsrle_mono_tuning.argtypes = [u32, u32, u32]
-    L.hsrle_mono_encode_stats.restype = None
-    L.hsrle_mono_encode_stats.argtypes = [ctypes.POINTER(u32)]
-    L.hsrle_split_sub_block_size.restype = u32
-    L.hsrle_split_sub_block_size.argtypes = [ctypes.POINTER(ContainerInfo), u32]
-    L.hsrle_decompress_split_workspace_size.restype = u64
-    L.hsrle_decompress_split_workspace_size.argtypes = [ctypes.POINTER(ContainerInfo), u32, u32]
-    L.hsrle_decompress_split_dev_async.restype = ci
-    L.hsrle_decompress_split_dev_async.argtypes = [vp, ctypes.POINTER(ContainerInfo), u32, u32, vp, u64, vp, vp, u64, u32, vp]
-    if hasattr(L, "hsrle_decompress_wave_dev_async"):                    # experiment builds only
-        L.hsrle_decompress_wave_dev_async.restype = ci
-        L.hsrle_decompress_wave_dev_async.argtypes = [vp, ctypes.POINTER(ContainerInfo), u32, u32, vp, u64, vp, vp]
-    L.hsrle_hash_blocks_dev_async.restype = ci
-    L.hsrle_hash_blocks_dev_async.argtypes = [vp, ctypes.POINTER(ContainerInfo), u32, u32, vp, vp]
-    L.hsrle_synth_dev_async.restype = ci
-    L.hsrle_synth_dev_async.argtypes = [ci, ci, u64, vp, u64, vp]
-    L.hsrle_mmtf_workspace_size.restype = u64
-    L.hsrle_mmtf_workspace_size.argtypes = [ci, u64]
-    L.hsrle_mmtf_dev_async.restype = ci
-    L.hsrle_mmtf_dev_async.argtypes = [ci, ci, vp, u64, vp, vp, u64, vp]
-    L.hsrle_mmtf_tuning.restype = None
-    L.hsrle_mmtf_tuning.argtypes = [u32]
-    for nm in ("mmtf_bounds", "bitmmtf_bounds"):
-        getattr(L, nm).restype = u32
-        getattr(L, nm).argtypes = [u32]
-    for nm in ("rle8_mmtf128_compress_bounds", "rle8_mmtf256_compress_bounds"):
-        getattr(L, nm).restype = u32
-        getattr(L, nm).argtypes = [u32]
-    L.hsrle_rle8_mmtf128_workspace_size.restype = u64
-    L.hsrle_rle8_mmtf128_workspace_size.argtypes = [ci, u64]
-    L.hsrle_rle8_mmtf128_compress_dev_async.restype = ci
-    L.hsrle_rle8_mmtf128_compress_dev_async.argtypes = [vp, u64, vp, u64, vp, vp, vp, u64, vp]
-    L.hsrle_rle8_mmtf128_decompress_dev_async.restype = ci
-    L.hsrle_rle8_mmtf128_decompress_dev_async.argtypes = [vp, u64, vp, u64, vp, vp, u64, vp]
-    L.hsrle_rle8_mmtf_tuning.restype = None
-    L.hsrle_rle8_mmtf_tuning.argtypes = [u32]
-    L.rle8_sh_bounds.restype = u32
-    L.rle8_sh_bounds.argtypes = [u32]
-    L.hsrle_rle8_sh_workspace_size.restype = u64
-    L.hsrle_rle8_sh_workspace_size.argtypes = [ci, u64]
-    L.hsrle_rle8_sh_capacity.restype = u64
-    L.hsrle_rle8_sh_capacity.argtypes = [u64]
-    L.hsrle_rle8_sh_compress_dev_async.restype = ci
-    L.hsrle_rle8_sh_compress_dev_async.argtypes = [vp, u64, vp, u64, vp, vp, vp, u64, vp]
-    L.hsrle_rle8_sh_decompress_dev_async.restype = ci
-    L.hsrle_rle8_sh_decompress_dev_async.argtypes = [vp, u64, vp, u64, vp, vp, u64, vp]
-    L.hsrle_rle8_sh_tuning.restype = None
-    L.hsrle_rle8_sh_tuning.argtypes = [u32, u32, u32]
-    L.hsrle_rle8_sh_blocks_bound.restype = u64
-    L.hsrle_rle8_sh_blocks_bound.argtypes = [u64, u32]
-    L.hsrle_rle8_sh_blocks_workspace_size.restype = u64
-    L.hsrle_rle8_sh_blocks_workspace_size.argtypes = [ci, u64, u32]
-    L.hsrle_rle8_sh_blocks_info_host.restype = ci
-    L.hsrle_rle8_sh_blocks_info_host.argtypes = [vp, u64, ctypes.POINTER(Rle8ShBlocksInfo)]
-    L.hsrle_rle8_sh_blocks_info_dev.restype = ci
-    L.hsrle_rle8_sh_blocks_info_dev.argtypes = [vp, u64, ctypes.POINTER(Rle8ShBlocksInfo), vp]
-    L.hsrle_rle8_sh_compress_blocks_dev_async.restype = ci
-    L.hsrle_rle8_sh_compress_blocks_dev_async.argtypes = [vp, u64, u32, vp, u64, vp, vp, vp, u64, vp]
-    L.hsrle_rle8_sh_decompress_blocks_dev_async.restype = ci
-    L.hsrle_rle8_sh_decompress_blocks_dev_async.argtypes = [vp, ctypes.POINTER(Rle8ShBlocksInfo), u32, u32, vp, u64, vp, vp, u64, vp]
-    L.hsrle_rle8_sh_compress_blocks_host.restype = ci
-    L.hsrle_rle8_sh_compress_blocks_host.argtypes = [vp, u64, u32, vp, u64, ctypes.POINTER(u64)]
-    L.hsrle_rle8_sh_decompress_blocks_host.restype = ci
-    L.hsrle_rle8_sh_decompress_blocks_host.argtypes = [vp, u64, vp, u64, ctypes.POINTER(u64)]
-    L.hsrle_rle8_sh_blocks_tuning.restype = None
-    L.hsrle_rle8_sh_blocks_tuning.argtypes = [u32]
-    _LIB = L
-    return L
+    _LIB = declare(ctypes.CDLL(LIB_PATH))
+    return _LIB
 
 
 def lib():
@@ -364,10 +382,7 @@ def mono_compress_dev(codec, src, dst=None, workspace=None, return_chunks=False)
     if workspace is None or workspace.numel() < need:
         workspace = _scratch(need, src.device)
     size, chunks = ctypes.c_uint32(0), ctypes.c_uint32(0)
-    rc = _lib().hsrle_compress_mono_dev(cid, ctypes.c_void_p(src.data_ptr()), n, ctypes.c_void_p(dst.data_ptr()), dst.numel(), ctypes.c_void_p(workspace.data_ptr()),
-                                        workspace.numel(), ctypes.byref(size), ctypes.byref(chunks), _stream_ptr())
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_compress_mono_dev")
+    _call("hsrle_compress_mono_dev", cid, src, n, dst, dst.numel(), workspace, workspace.numel(), ctypes.byref(size), ctypes.byref(chunks))
     return (dst[: size.value], chunks.value) if return_chunks else dst[: size.value]
 
 
@@ -392,10 +407,7 @@ def mono_compress_dev_async(codec, src, dst, workspace, size_out=None):
     synchronises (can be captured in a HIP graph).  dst (>= compress_bounds(n) bytes), workspace (>= hsrle_compress_mono_workspace_size) and size_out
     (uint32[1] or None) are CUDA tensors the caller owns; the stream's size is also in bytes 4 .. 7 of dst once the stream has run."""
     _mono_encode_args("hsrle_compress_mono_dev_async", src, dst, workspace, size_out)
-    rc = _lib().hsrle_compress_mono_dev_async(codec_id(codec), ctypes.c_void_p(src.data_ptr()), src.numel(), ctypes.c_void_p(dst.data_ptr()), dst.numel(),
-                                              ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), ctypes.c_void_p(size_out.data_ptr() if size_out is not None else None), _stream_ptr())
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_compress_mono_dev_async")
+    _call("hsrle_compress_mono_dev_async", codec_id(codec), src, src.numel(), dst, dst.numel(), workspace, workspace.numel(), size_out)
 
 
 MONO_ENCODE_FAILED = 4
@@ -410,11 +422,7 @@ def mono_compress_dev_enqueue(codec, src, dst, workspace, status, size_out=None)
     if status is None:
         raise HsrleError(ERR_ARGUMENT, "hsrle_compress_mono_dev_enqueue: status is required")
     _mono_encode_args("hsrle_compress_mono_dev_enqueue", src, dst, workspace, size_out, status)
-    rc = _lib().hsrle_compress_mono_dev_enqueue(codec_id(codec), ctypes.c_void_p(src.data_ptr()), src.numel(), ctypes.c_void_p(dst.data_ptr()), dst.numel(),
-                                                ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), ctypes.c_void_p(size_out.data_ptr() if size_out is not None else None),
-                                                ctypes.c_void_p(status.data_ptr()), _stream_ptr())
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_compress_mono_dev_enqueue")
+    _call("hsrle_compress_mono_dev_enqueue", codec_id(codec), src, src.numel(), dst, dst.numel(), workspace, workspace.numel(), size_out, status)
 
 
 def mono_compress_workspace_size(codec, n):
@@ -444,10 +452,7 @@ def mono_decompress_dev(codec, stream_tensor, dst=None, workspace=None, return_s
         workspace = _scratch(max(need, 256), stream_tensor.device)
     n = ctypes.c_uint32(0)
     stats = (ctypes.c_uint32 * 4)()
-    rc = _lib().hsrle_decompress_mono_dev(cid, ctypes.c_void_p(stream_tensor.data_ptr()), csize, ctypes.c_void_p(dst.data_ptr()), dst.numel(),
-                                          ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), ctypes.byref(n), stats, _stream_ptr())
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_decompress_mono_dev")
+    _call("hsrle_decompress_mono_dev", cid, stream_tensor, csize, dst, dst.numel(), workspace, workspace.numel(), ctypes.byref(n), stats)
     return (dst[: n.value], tuple(stats)) if return_stats else dst[: n.value]
 
 
@@ -463,10 +468,7 @@ def mono_decompress_dev_async(codec, stream_tensor, header16, dst, workspace, st
     header16 = bytes(header16[:16]).ljust(16, b"\0")
     csize = int.from_bytes(header16[4:8], "little") if stream_size is None else int(stream_size)
     n = ctypes.c_uint32(0)
-    rc = _lib().hsrle_decompress_mono_dev_async(codec_id(codec), ctypes.c_void_p(stream_tensor.data_ptr()), header16, csize, ctypes.c_void_p(dst.data_ptr()), dst.numel(),
-                                                ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), ctypes.byref(n), ctypes.c_void_p(status.data_ptr()), _stream_ptr())
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_decompress_mono_dev_async")
+    _call("hsrle_decompress_mono_dev_async", codec_id(codec), stream_tensor, header16, csize, dst, dst.numel(), workspace, workspace.numel(), ctypes.byref(n), status)
     return n.value
 
 
@@ -503,10 +505,7 @@ def mono_index_build(codec, stream_tensor, spacing=0, index=None, workspace=None
         workspace = _scratch(max(need, 256), stream_tensor.device)
     _check_u8_cuda(workspace, "workspace")
     info = MonoIndexInfo()
-    rc = _lib().hsrle_mono_index_build_dev(cid, ctypes.c_void_p(stream_tensor.data_ptr()), ssize, spacing, ctypes.c_void_p(index.data_ptr()), index.numel(),
-                                           ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), ctypes.byref(info), _stream_ptr())
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_mono_index_build_dev")
+    _call("hsrle_mono_index_build_dev", cid, stream_tensor, ssize, spacing, index, index.numel(), workspace, workspace.numel(), ctypes.byref(info))
     return index[: info.indexBytes], info
 
 
@@ -533,20 +532,14 @@ def mono_decompress_range_dev_async(stream_tensor, index, info, offset, length, 
         _check_u8_cuda(t, what)
     if status.numel() < 4:
         raise TypeError("status must hold 4 bytes")
-    rc = _lib().hsrle_mono_decompress_range_dev_async(ctypes.c_void_p(stream_tensor.data_ptr()), ctypes.c_void_p(index.data_ptr()), ctypes.byref(info), offset, length,
-                                                      ctypes.c_void_p(dst.data_ptr()), dst.numel(), ctypes.c_void_p(status.data_ptr()), _stream_ptr(stream))
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_mono_decompress_range_dev_async")
+    _call("hsrle_mono_decompress_range_dev_async", stream_tensor, index, ctypes.byref(info), offset, length, dst, dst.numel(), status, stream=stream)
 
 
 def call_dropin(name, data, out_cap):
     """Call one of the rle.h-named exports directly, e.g. call_dropin("rle8_packed_multi_compress", data, cap)."""
-    f = getattr(_lib(), name)
-    f.restype = ctypes.c_uint32
-    f.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32]
     data = bytes(data)
     out = ctypes.create_string_buffer(max(out_cap, 1))
-    size = f(data, len(data), out, out_cap)
+    size = getattr(_lib(), name)(data, len(data), out, out_cap)
     return size, out.raw[:size]
 
 
@@ -559,6 +552,20 @@ def _stream_ptr(stream=None):
 
     s = stream if stream is not None else torch.cuda.current_stream()
     return ctypes.c_void_p(s.cuda_stream)
+
+
+def _ptr(t):
+    """What a pointer parameter takes: a tensor's address; None, bytes, byref(...) and integers pass as they are."""
+    return ctypes.c_void_p(t.data_ptr()) if hasattr(t, "data_ptr") else t
+
+
+def _call(name, *args, stream=None, raises=True):
+    """One device call by name: tensors become their addresses, sizes and the rest pass as they are, the stream (None: the current one) goes last.
+    Raises HsrleError(rc, name) unless the code is OK; raises=False returns it."""
+    rc = getattr(_lib(), name)(*[_ptr(a) for a in args], _stream_ptr(stream))
+    if raises and rc != OK:
+        raise HsrleError(rc, name)
+    return rc
 
 
 def _scratch(n, device):
@@ -582,14 +589,9 @@ def compress_async(codec, src, dst, block_size=DEFAULT_BLOCK_SIZE, workspace=Non
     """Enqueue compression of `src` into the container buffer `dst` (capacity >= container_bound)."""
     _check_u8_cuda(src, "src")
     _check_u8_cuda(dst, "dst")
-    wptr, wsize = (None, 0)
     if workspace is not None:
         _check_u8_cuda(workspace, "workspace")
-        wptr, wsize = ctypes.c_void_p(workspace.data_ptr()), workspace.numel()
-    rc = _lib().hsrle_compress_dev_async(codec_id(codec), ctypes.c_void_p(src.data_ptr()), src.numel(), ctypes.c_void_p(dst.data_ptr()), dst.numel(),
-                                         block_size, wptr, wsize, _stream_ptr(stream))
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_compress_dev_async")
+    _call("hsrle_compress_dev_async", codec_id(codec), src, src.numel(), dst, dst.numel(), block_size, workspace, workspace.numel() if workspace is not None else 0, stream=stream)
 
 
 def compress(codec, src, block_size=DEFAULT_BLOCK_SIZE, dst=None):
@@ -600,10 +602,7 @@ def compress(codec, src, block_size=DEFAULT_BLOCK_SIZE, dst=None):
     if dst is None:
         dst = torch.empty(container_bound(src.numel(), block_size), dtype=torch.uint8, device=src.device)
     total = ctypes.c_uint64(0)
-    rc = _lib().hsrle_compress_dev(codec_id(codec), ctypes.c_void_p(src.data_ptr()), src.numel(), ctypes.c_void_p(dst.data_ptr()), dst.numel(), block_size,
-                                   ctypes.byref(total), _stream_ptr())
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_compress_dev")
+    _call("hsrle_compress_dev", codec_id(codec), src, src.numel(), dst, dst.numel(), block_size, ctypes.byref(total))
     container = dst[: total.value]
     return container, container_info(container)
 
@@ -629,11 +628,7 @@ def decompress_async(container, info, dst, status=None, first_block=0, block_cou
     _check_u8_cuda(dst, "dst")
     if block_count is None:
         block_count = info.blockCount - first_block
-    sp = ctypes.c_void_p(status.data_ptr()) if status is not None else None
-    rc = _lib().hsrle_decompress_blocks_dev_async(ctypes.c_void_p(container.data_ptr()), ctypes.byref(info), first_block, block_count,
-                                                  ctypes.c_void_p(dst.data_ptr()), dst.numel(), sp, _stream_ptr(stream))
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_decompress_blocks_dev_async")
+    _call("hsrle_decompress_blocks_dev_async", container, ctypes.byref(info), first_block, block_count, dst, dst.numel(), status, stream=stream)
 
 
 def decompress_range_dev_async(container, info, offset, length, dst, status, stream=None):
@@ -643,10 +638,7 @@ def decompress_range_dev_async(container, info, offset, length, dst, status, str
         _check_u8_cuda(t, what)
     if status.numel() < 4:
         raise TypeError("status must hold 4 bytes")
-    rc = _lib().hsrle_decompress_range_dev_async(ctypes.c_void_p(container.data_ptr()), ctypes.byref(info), offset, length, ctypes.c_void_p(dst.data_ptr()), dst.numel(),
-                                                 ctypes.c_void_p(status.data_ptr()), _stream_ptr(stream))
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_decompress_range_dev_async")
+    _call("hsrle_decompress_range_dev_async", container, ctypes.byref(info), offset, length, dst, dst.numel(), status, stream=stream)
 
 
 def hash_blocks(container, info, first_block=0, block_count=None):
@@ -657,9 +649,7 @@ def hash_blocks(container, info, first_block=0, block_count=None):
     if block_count is None:
         block_count = info.blockCount - first_block
     out = torch.empty(block_count, dtype=torch.int64, device=container.device)
-    rc = _lib().hsrle_hash_blocks_dev_async(ctypes.c_void_p(container.data_ptr()), ctypes.byref(info), first_block, block_count, ctypes.c_void_p(out.data_ptr()), _stream_ptr())
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_hash_blocks_dev_async")
+    _call("hsrle_hash_blocks_dev_async", container, ctypes.byref(info), first_block, block_count, out)
     return out
 
 
@@ -673,12 +663,8 @@ def decompress_split_async(container, info, dst, workspace, status=None, sub_blo
     _check_u8_cuda(dst, "dst")
     if block_count is None:
         block_count = info.blockCount - first_block
-    sp = ctypes.c_void_p(status.data_ptr()) if status is not None else None
-    wp, wn = (ctypes.c_void_p(workspace.data_ptr()), workspace.numel()) if workspace is not None else (None, 0)
-    rc = _lib().hsrle_decompress_split_dev_async(ctypes.c_void_p(container.data_ptr()), ctypes.byref(info), first_block, block_count, ctypes.c_void_p(dst.data_ptr()), dst.numel(),
-                                                 sp, wp, wn, sub_block, _stream_ptr(stream))
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_decompress_split_dev_async")
+    _call("hsrle_decompress_split_dev_async", container, ctypes.byref(info), first_block, block_count, dst, dst.numel(), status, workspace,
+          workspace.numel() if workspace is not None else 0, sub_block, stream=stream)
 
 
 def decompress_wave_async(container, info, dst, status=None, first_block=0, block_count=None, stream=None):
@@ -689,11 +675,7 @@ def decompress_wave_async(container, info, dst, status=None, first_block=0, bloc
     _check_u8_cuda(dst, "dst")
     if block_count is None:
         block_count = info.blockCount - first_block
-    sp = ctypes.c_void_p(status.data_ptr()) if status is not None else None
-    rc = _lib().hsrle_decompress_wave_dev_async(ctypes.c_void_p(container.data_ptr()), ctypes.byref(info), first_block, block_count, ctypes.c_void_p(dst.data_ptr()), dst.numel(),
-                                                sp, _stream_ptr(stream))
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_decompress_wave_dev_async")
+    _call("hsrle_decompress_wave_dev_async", container, ctypes.byref(info), first_block, block_count, dst, dst.numel(), status, stream=stream)
 
 
 def decompress(container, dst=None):
@@ -704,9 +686,7 @@ def decompress(container, dst=None):
     if dst is None:
         dst = torch.empty(info.uncompressedSize, dtype=torch.uint8, device=container.device)
     n = ctypes.c_uint64(0)
-    rc = _lib().hsrle_decompress_dev(ctypes.c_void_p(container.data_ptr()), container.numel(), ctypes.c_void_p(dst.data_ptr()), dst.numel(), ctypes.byref(n), _stream_ptr())
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_decompress_dev")
+    _call("hsrle_decompress_dev", container, container.numel(), dst, dst.numel(), ctypes.byref(n))
     return dst[: n.value]
 
 
@@ -716,9 +696,7 @@ def synth(kind, symbol_bytes, seed, size, device="cuda", out=None):
 
     if out is None:
         out = torch.empty(size, dtype=torch.uint8, device=device)
-    rc = _lib().hsrle_synth_dev_async(kind, symbol_bytes, seed, ctypes.c_void_p(out.data_ptr()), size, _stream_ptr())
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_synth_dev_async")
+    _call("hsrle_synth_dev_async", kind, symbol_bytes, seed, out, size)
     return out
 
 
@@ -737,20 +715,11 @@ def split_container(container_bytes):
 # rle8m: the reference's own GPU decode path (include/hsrle.h)
 
 
-class Rle8mInfo(ctypes.Structure):
-    _fields_ = [("compressedSize", ctypes.c_uint32), ("uncompressedSize", ctypes.c_uint32), ("sections", ctypes.c_uint32)]
-
-
 def rle8m_info(stream_tensor):
     """Header fields of a device-resident rle8m stream (synchronises)."""
     _check_u8_cuda(stream_tensor, "stream")
     info = Rle8mInfo()
-    L = _lib()
-    L.hsrle_rle8m_info_dev.restype = ctypes.c_int
-    L.hsrle_rle8m_info_dev.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
-    rc = L.hsrle_rle8m_info_dev(ctypes.c_void_p(stream_tensor.data_ptr()), stream_tensor.numel(), ctypes.byref(info), _stream_ptr())
-    if rc != 0:
-        raise HsrleError(rc, "hsrle_rle8m_info_dev")
+    _call("hsrle_rle8m_info_dev", stream_tensor, stream_tensor.numel(), ctypes.byref(info))
     return info
 
 
@@ -758,24 +727,15 @@ def rle8m_decompress_async(stream_tensor, info, dst, status=None, stream=None):
     """Enqueue the decode of a device-resident rle8m stream into `dst` (uint8 CUDA tensor); `status` optional int32 tensor."""
     _check_u8_cuda(stream_tensor, "stream")
     _check_u8_cuda(dst, "dst")
-    L = _lib()
-    L.hsrle_rle8m_decompress_dev_async.restype = ctypes.c_int
-    L.hsrle_rle8m_decompress_dev_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
-    sp = ctypes.c_void_p(status.data_ptr()) if status is not None else None
-    rc = L.hsrle_rle8m_decompress_dev_async(ctypes.c_void_p(stream_tensor.data_ptr()), ctypes.byref(info), ctypes.c_void_p(dst.data_ptr()), dst.numel(), sp, _stream_ptr(stream))
-    if rc != 0:
-        raise HsrleError(rc, "hsrle_rle8m_decompress_dev_async")
+    _call("hsrle_rle8m_decompress_dev_async", stream_tensor, ctypes.byref(info), dst, dst.numel(), status, stream=stream)
 
 
 def rle8m_compress_dropin(sections, data):
     """rle8m_compress(subSections, pIn, inSize, pOut, outSize) of the library (host pointers); returns the stream or None (the reference's 0)."""
-    L = _lib()
-    L.rle8m_compress_bounds.restype = ctypes.c_uint32
-    L.rle8m_compress.restype = ctypes.c_uint32
     data = bytes(data)
-    cap = L.rle8m_compress_bounds(ctypes.c_uint32(sections), ctypes.c_uint32(len(data)))
+    cap = rle8m_bounds(sections, len(data))
     out = ctypes.create_string_buffer(cap + 64)
-    size = L.rle8m_compress(ctypes.c_uint32(sections), data, ctypes.c_uint32(len(data)), out, ctypes.c_uint32(cap))
+    size = _lib().rle8m_compress(sections, data, len(data), out, cap)
     return out.raw[:size] if size else None
 
 
@@ -784,39 +744,24 @@ def rle8m_compress_async(src, sections, dst, workspace, status=None, stream=None
     _check_u8_cuda(src, "src")
     _check_u8_cuda(dst, "dst")
     _check_u8_cuda(workspace, "workspace")
-    L = _lib()
-    L.hsrle_rle8m_compress_dev_async.restype = ctypes.c_int
-    L.hsrle_rle8m_compress_dev_async.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
-    sp = ctypes.c_void_p(status.data_ptr()) if status is not None else None
-    rc = L.hsrle_rle8m_compress_dev_async(ctypes.c_void_p(src.data_ptr()), src.numel(), sections, ctypes.c_void_p(dst.data_ptr()), dst.numel(),
-                                          ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), sp, _stream_ptr(stream))
-    if rc != 0:
-        raise HsrleError(rc, "hsrle_rle8m_compress_dev_async")
+    _call("hsrle_rle8m_compress_dev_async", src, src.numel(), sections, dst, dst.numel(), workspace, workspace.numel(), status, stream=stream)
 
 
 def rle8m_workspace_size(in_size, sections):
-    L = _lib()
-    L.hsrle_rle8m_compress_workspace_size.restype = ctypes.c_uint64
-    return int(L.hsrle_rle8m_compress_workspace_size(ctypes.c_uint32(in_size), ctypes.c_uint32(sections)))
+    return int(_lib().hsrle_rle8m_compress_workspace_size(in_size, sections))
 
 
 def rle8m_bounds(sections, in_size):
-    L = _lib()
-    L.rle8m_compress_bounds.restype = ctypes.c_uint32
-    return int(L.rle8m_compress_bounds(ctypes.c_uint32(sections), ctypes.c_uint32(in_size)))
+    return int(_lib().rle8m_compress_bounds(sections, in_size))
 
 
 def low_entropy_bounds(in_size):
-    L = _lib()
-    L.rle8_low_entropy_compress_bounds.restype = ctypes.c_uint32
-    return int(L.rle8_low_entropy_compress_bounds(ctypes.c_uint32(in_size)))
+    return int(_lib().rle8_low_entropy_compress_bounds(in_size))
 
 
 def low_entropy_workspace_size(n):
     """hsrle_low_entropy_workspace_size: bytes of device workspace for the encode of `n` input bytes (0 for n == 0)."""
-    L = _lib()
-    L.hsrle_low_entropy_workspace_size.restype = ctypes.c_uint64
-    return int(L.hsrle_low_entropy_workspace_size(ctypes.c_uint32(n)))
+    return int(_lib().hsrle_low_entropy_workspace_size(n))
 
 
 def low_entropy_compress_dev(src, variant, dst, workspace, status, stream=None):
@@ -825,13 +770,7 @@ def low_entropy_compress_dev(src, variant, dst, workspace, status, stream=None):
     stream's size is its first u32.  Returns the status code (OK, ERR_CAPACITY, ERR_ARGUMENT, ...): returned, not raised."""
     for t, what in ((src, "src"), (dst, "dst"), (workspace, "workspace")):
         _check_u8_cuda(t, what)
-    L = _lib()
-    L.hsrle_low_entropy_compress_dev_async.restype = ctypes.c_int
-    L.hsrle_low_entropy_compress_dev_async.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
-                                                       ctypes.c_void_p, ctypes.c_void_p]
-    sp = ctypes.c_void_p(status.data_ptr()) if status is not None else None
-    return int(L.hsrle_low_entropy_compress_dev_async(ctypes.c_void_p(src.data_ptr()), src.numel(), variant, ctypes.c_void_p(dst.data_ptr()), dst.numel(),
-                                                      ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), sp, _stream_ptr(stream)))
+    return int(_call("hsrle_low_entropy_compress_dev_async", src, src.numel(), variant, dst, dst.numel(), workspace, workspace.numel(), status, stream=stream, raises=False))
 
 
 def encode_stats_words(workspace):
@@ -843,9 +782,7 @@ def encode_stats_words(workspace):
 
 def low_entropy_decompress_workspace_size(stream_size):
     """hsrle_low_entropy_decompress_workspace_size: bytes of device workspace for the decode of an unsectioned stream of `stream_size` bytes."""
-    L = _lib()
-    L.hsrle_low_entropy_decompress_workspace_size.restype = ctypes.c_uint64
-    return int(L.hsrle_low_entropy_decompress_workspace_size(ctypes.c_uint64(stream_size)))
+    return int(_lib().hsrle_low_entropy_decompress_workspace_size(stream_size))
 
 
 def low_entropy_decompress_dev(stream_tensor, dst, workspace, stream=None):
@@ -853,12 +790,8 @@ def low_entropy_decompress_dev(stream_tensor, dst, workspace, stream=None):
     Returns (status code, uncompressed size): OK, ERR_FORMAT for a stream that is refused, ... -- the code is returned, not raised."""
     for t, what in ((stream_tensor, "stream"), (dst, "dst"), (workspace, "workspace")):
         _check_u8_cuda(t, what)
-    L = _lib()
-    L.hsrle_low_entropy_decompress_dev.restype = ctypes.c_int
-    L.hsrle_low_entropy_decompress_dev.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
     size = ctypes.c_uint32(0)
-    rc = L.hsrle_low_entropy_decompress_dev(ctypes.c_void_p(stream_tensor.data_ptr()), stream_tensor.numel(), ctypes.c_void_p(dst.data_ptr()), dst.numel(),
-                                            ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), ctypes.byref(size), _stream_ptr(stream))
+    rc = _call("hsrle_low_entropy_decompress_dev", stream_tensor, stream_tensor.numel(), dst, dst.numel(), workspace, workspace.numel(), ctypes.byref(size), stream=stream, raises=False)
     return int(rc), int(size.value)
 
 
@@ -892,10 +825,7 @@ def mmtf_dev(transform, decode, src, dst, ws, stream=None):
         _check_u8_cuda(t, what)
     if dst.numel() < src.numel():
         raise TypeError("dst is shorter than src")
-    rc = _lib().hsrle_mmtf_dev_async(transform, 1 if decode else 0, ctypes.c_void_p(src.data_ptr()), src.numel(), ctypes.c_void_p(dst.data_ptr()),
-                                     ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(stream))
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_mmtf_dev_async")
+    _call("hsrle_mmtf_dev_async", transform, 1 if decode else 0, src, src.numel(), dst, ws, ws.numel(), stream=stream)
 
 
 def mmtf_bounds(n):
@@ -963,11 +893,7 @@ def rle8_mmtf128_compress_dev(src, dst, out_size, status, ws, stream=None):
     suffice).  out_size / status: CUDA int32 tensors of one element, they receive the stream size and RLE8_MMTF_DONE / RLE8_MMTF_CAPACITY."""
     for t, what in ((src, "src"), (dst, "dst"), (ws, "ws")):
         _check_u8_cuda(t, what)
-    rc = _lib().hsrle_rle8_mmtf128_compress_dev_async(ctypes.c_void_p(src.data_ptr()), src.numel(), ctypes.c_void_p(dst.data_ptr()), dst.numel(),
-                                                      ctypes.c_void_p(out_size.data_ptr()), ctypes.c_void_p(status.data_ptr()),
-                                                      ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(stream))
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_rle8_mmtf128_compress_dev_async")
+    _call("hsrle_rle8_mmtf128_compress_dev_async", src, src.numel(), dst, dst.numel(), out_size, status, ws, ws.numel(), stream=stream)
 
 
 def rle8_mmtf128_decompress_dev(src, dst, status, ws, stream=None):
@@ -975,10 +901,7 @@ def rle8_mmtf128_decompress_dev(src, dst, status, ws, stream=None):
     uncompressed size.  status: CUDA int32 tensor of one element, receives RLE8_MMTF_DONE / RLE8_MMTF_MALFORMED."""
     for t, what in ((src, "src"), (dst, "dst"), (ws, "ws")):
         _check_u8_cuda(t, what)
-    rc = _lib().hsrle_rle8_mmtf128_decompress_dev_async(ctypes.c_void_p(src.data_ptr()), src.numel(), ctypes.c_void_p(dst.data_ptr()), dst.numel(),
-                                                        ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(stream))
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_rle8_mmtf128_decompress_dev_async")
+    _call("hsrle_rle8_mmtf128_decompress_dev_async", src, src.numel(), dst, dst.numel(), status, ws, ws.numel(), stream=stream)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1033,11 +956,7 @@ def rle8_sh_compress_dev(src, dst, out_size, status, ws, stream=None):
     RLE8_SH_DONE / RLE8_SH_CAPACITY."""
     for t, what in ((src, "src"), (dst, "dst"), (ws, "ws")):
         _check_u8_cuda(t, what)
-    rc = _lib().hsrle_rle8_sh_compress_dev_async(ctypes.c_void_p(src.data_ptr()), src.numel(), ctypes.c_void_p(dst.data_ptr()), dst.numel(),
-                                                 ctypes.c_void_p(out_size.data_ptr()), ctypes.c_void_p(status.data_ptr()),
-                                                 ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(stream))
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_rle8_sh_compress_dev_async")
+    _call("hsrle_rle8_sh_compress_dev_async", src, src.numel(), dst, dst.numel(), out_size, status, ws, ws.numel(), stream=stream)
 
 
 def rle8_sh_decompress_dev(src, dst, status, ws, stream=None):
@@ -1045,10 +964,7 @@ def rle8_sh_decompress_dev(src, dst, status, ws, stream=None):
     uncompressed size.  status: CUDA int32 tensor of one element, receives RLE8_SH_DONE / RLE8_SH_MALFORMED."""
     for t, what in ((src, "src"), (dst, "dst"), (ws, "ws")):
         _check_u8_cuda(t, what)
-    rc = _lib().hsrle_rle8_sh_decompress_dev_async(ctypes.c_void_p(src.data_ptr()), src.numel(), ctypes.c_void_p(dst.data_ptr()), dst.numel(),
-                                                   ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(stream))
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_rle8_sh_decompress_dev_async")
+    _call("hsrle_rle8_sh_decompress_dev_async", src, src.numel(), dst, dst.numel(), status, ws, ws.numel(), stream=stream)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1091,11 +1007,7 @@ def rle8_sh_blocks_compress_dev(src, dst, out_size, status, ws, block_size=0, st
     status: CUDA int32 tensor of one element, receives RLE8_SH_DONE / RLE8_SH_CAPACITY."""
     for t, what in ((src, "src"), (dst, "dst"), (ws, "ws")):
         _check_u8_cuda(t, what)
-    rc = _lib().hsrle_rle8_sh_compress_blocks_dev_async(ctypes.c_void_p(src.data_ptr()), src.numel(), block_size, ctypes.c_void_p(dst.data_ptr()), dst.numel(),
-                                                        ctypes.c_void_p(out_size.data_ptr()), ctypes.c_void_p(status.data_ptr()),
-                                                        ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(stream))
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_rle8_sh_compress_blocks_dev_async")
+    _call("hsrle_rle8_sh_compress_blocks_dev_async", src, src.numel(), block_size, dst, dst.numel(), out_size, status, ws, ws.numel(), stream=stream)
 
 
 def rle8_sh_blocks_decompress_dev(container, info, dst, status, ws, first_block=0, block_count=None, stream=None):
@@ -1105,11 +1017,7 @@ def rle8_sh_blocks_decompress_dev(container, info, dst, status, ws, first_block=
     for t, what in ((container, "container"), (dst, "dst"), (ws, "ws")):
         _check_u8_cuda(t, what)
     count = info.blockCount - first_block if block_count is None else block_count
-    rc = _lib().hsrle_rle8_sh_decompress_blocks_dev_async(ctypes.c_void_p(container.data_ptr()), ctypes.byref(info), first_block, count,
-                                                          ctypes.c_void_p(dst.data_ptr()), dst.numel(), ctypes.c_void_p(status.data_ptr()),
-                                                          ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr(stream))
-    if rc != OK:
-        raise HsrleError(rc, "hsrle_rle8_sh_decompress_blocks_dev_async")
+    _call("hsrle_rle8_sh_decompress_blocks_dev_async", container, ctypes.byref(info), first_block, count, dst, dst.numel(), status, ws, ws.numel(), stream=stream)
 
 
 def rle8_sh_blocks_compress_host(data, block_size=0, out_cap=None):

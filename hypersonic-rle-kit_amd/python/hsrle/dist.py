@@ -247,9 +247,7 @@ def c_comm_ranks(group=None):
 
     import hsrle
 
-    L = hsrle.lib()
-    L.hsrle_rccl_comm_ranks.restype = ctypes.c_int
-    L.hsrle_rccl_comm_ranks.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    L = hsrle.lib()                                                      # (declared from hsrle.SIGNATURES, like every function of the library)
     world, rank = ctypes.c_int(0), ctypes.c_int(0)
     rc = L.hsrle_rccl_comm_ranks(c_comm(group), ctypes.byref(world), ctypes.byref(rank))
     if rc != 0:
@@ -276,9 +274,6 @@ def gather_container_c(local_container, total_uncompressed_size, root=0, group=N
     import hsrle
 
     L = hsrle.lib()
-    L.hsrle_gather_container_rccl.restype = ctypes.c_int
-    L.hsrle_gather_container_rccl.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
-                                              ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
     comm = c_comm(group)
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -303,9 +298,6 @@ def scatter_container_c(container, shard_capacity, root=0, group=None):
     import hsrle
 
     L = hsrle.lib()
-    L.hsrle_scatter_container_rccl.restype = ctypes.c_int
-    L.hsrle_scatter_container_rccl.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
-                                               ctypes.c_void_p]
     comm = c_comm(group)
     rank = dist.get_rank(group)
     dev = torch.device("cuda", torch.cuda.current_device())

@@ -5,29 +5,43 @@ import re
 
 import pytest
 
+import hsrle
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(REPO, "hypersonic-rle-kit_amd", "libhsrle_hip.so")
 HEADER = os.path.join(REPO, "include", "hsrle.h")
 
 
+def prototypes(experiments=False):
+    """{symbol: (return type, [parameter types])} of every function include/hsrle.h declares, its macros expanded.  A type is its base name without
+    const, with a * per pointer level (an array parameter is a pointer).  experiments: the declarations inside #ifdef HSRLE_EXPERIMENTS instead (not part
+    of the shipped library)."""
+    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S))
+    guarded = re.compile(r"#ifdef HSRLE_EXPERIMENTS(.*?)#endif", re.S)
+    text = "".join(guarded.findall(text)) if experiments else guarded.sub("", text)
+    text = text.replace("\\\n", " ")
+    macros = {m.group(1): (m.group(2), m.group(3)) for m in re.finditer(r"^#define\s+(\w+)\((\w+)\)\s+(.*)$", text, flags=re.M)}   # the drop-in declarators: one parameter each
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    call = re.compile(r"\b(%s)\((\w+)\)" % "|".join(macros or ["(?!)"]))
+    while call.search(text):
+        text = call.sub(lambda m: re.sub(r"\s*##\s*", "", re.sub(r"\b%s\b" % macros[m.group(1)][0], m.group(2), macros[m.group(1)][1])), text)
+    text = re.sub(r"typedef\s+(?:struct|enum)[^{;]*\{.*?\}\s*\w+\s*;", "", text, flags=re.S)
+    text = re.sub(r'extern\s+"C"\s*\{', "", text)
+
+    def ctype(decl, named):
+        stars = decl.count("*") + decl.count("[")
+        words = re.sub(r"\[[^\]]*\]|\*|\bconst\b", " ", decl).split()
+        return " ".join(words[:-1] if named and len(words) > 1 else words) + "*" * stars
+
+    out = {}
+    for ret, name, params in re.findall(r"([\w\s\*]+?)\b(\w+)\s*\(([^()]*)\)\s*;", text):
+        params = [q.strip() for q in params.split(",") if q.strip() not in ("", "void")]
+        out[name] = (ctype(ret, False), [ctype(q, True) for q in params])
+    return out
+
+
 def declared_symbols():
-    text = open(HEADER).read()
-    text = re.sub(r"#ifdef HSRLE_EXPERIMENTS.*?#endif", "", text, flags=re.S)   # experiment builds only: not part of the shipped library
-    names = set(re.findall(r"\b((?:hsrle|rle)[A-Za-z0-9_]*)\s*\(", re.sub(r"/\*.*?\*/", "", text, flags=re.S)))
-    # macro-declared drop-in pairs
-    pairs = ["rle8_3symlut", "rle8_7symlut", "rle128_sym", "rle128_sym_packed", "rle128_byte", "rle128_byte_packed"]
-    for W in (16, 24, 32, 48, 64):
-        pairs += [f"rle{W}_{v}" for v in ("sym", "sym_packed", "byte", "byte_packed", "3symlut_sym", "7symlut_sym", "3symlut_byte", "7symlut_byte")]
-    pairs += ["rle8_multi_short", "rle8_single_short", "rle8_1symlut_short", "rle8_3symlut_short", "rle8_7symlut_short"]
-    for W in (16, 24, 32, 48, 64):
-        pairs += [f"rle{W}_{v}_short" for v in ("sym", "byte", "1symlut_sym", "1symlut_byte", "3symlut_sym", "3symlut_byte", "7symlut_sym", "7symlut_byte")]
-    for W in (16, 24, 32, 48, 64):
-        for k in (1, 3, 7):
-            names.add(f"rle{W}_{k}symlut_byte_short_compress_greedy")
-    for p in pairs:
-        names.add(p + "_compress")
-        names.add(p + "_decompress")
-    return sorted(n for n in names if not n.endswith("_t"))
+    return sorted(prototypes())
 
 
 @pytest.fixture(scope="module")
@@ -36,7 +50,7 @@ def lib():
         import subprocess
 
         subprocess.check_call(["make", "-s", "-j8", "-C", os.path.join(REPO, "hypersonic-rle-kit_amd")])
-    return ctypes.CDLL(LIB)
+    return hsrle.declare(ctypes.CDLL(LIB))
 
 
 def test_all_declared_symbols_are_exported(lib):
@@ -58,20 +72,14 @@ def test_reference_names_present(lib):
 
 def test_pure_host_helpers(lib):
     """Helpers that need no device."""
-    lib.rle_compress_bounds.restype = ctypes.c_uint32
-    assert lib.rle_compress_bounds(ctypes.c_uint32(1000)) == 1193
-    assert lib.rle_compress_bounds(ctypes.c_uint32((1 << 30) + 1)) == 0
-    lib.rle_decompress_additional_size.restype = ctypes.c_uint32
+    assert lib.rle_compress_bounds(1000) == 1193
+    assert lib.rle_compress_bounds((1 << 30) + 1) == 0
     assert lib.rle_decompress_additional_size() == 128
-    lib.hsrle_codec_from_name.restype = ctypes.c_int
-    lib.hsrle_codec_name.restype = ctypes.c_char_p
     for i in range(110):
         name = lib.hsrle_codec_name(i)
         assert lib.hsrle_codec_from_name(name) == i
     assert lib.hsrle_codec_from_name(b"rle8_packed_multi") == 1 and lib.hsrle_codec_from_name(b"rle64_3symlut_byte") == 44
     assert lib.hsrle_codec_from_name(b"nope") == -1
-    lib.hsrle_container_bound.restype = ctypes.c_uint64
-    lib.hsrle_container_bound.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
     assert lib.hsrle_container_bound(1 << 20, 4096) > (1 << 20)
     assert lib.hsrle_container_bound(1 << 20, 4000) == 0  # block size must be a multiple of 128
 
@@ -80,9 +88,6 @@ def test_encode_path_selection(lib):
     """hsrle_encode_path (no device): which encoder a container takes.  Big containers: one lane per block; small ones of 1 .. 4 KiB blocks: the
     run list encoders for the multi-symbol 8 bit codecs, the 2 .. 8 byte codecs and their Short family, the split encode for the rest that
     can be cut (Single, 128 bit and Greedy only with a workspace sized for the codec); other block sizes: split encode or ring."""
-    lib.hsrle_encode_path.restype = ctypes.c_int
-    lib.hsrle_encode_path.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32]
-    lib.hsrle_codec_from_name.restype = ctypes.c_int
     cid = lambda n: lib.hsrle_codec_from_name(n.encode())
     RING, SPLIT, RUN_LIST, PP = 0, 1, 2, 3
     frame = 88473600
@@ -119,10 +124,6 @@ def test_encode_path_selection(lib):
         assert lib.hsrle_encode_path(cid(name), frame, 4096) == RING, name          # (split only with a workspace sized for the codec -- the host cannot know)
     for name in ("rle16_1symlut_byte_short_greedy", "rle64_1symlut_byte_short_greedy", "rle8_single_short"):
         assert lib.hsrle_encode_path(cid(name), frame, 8192) == SPLIT, name         # round 4: their chunk encoders take the blocks of a container too
-    lib.hsrle_compress_workspace_size.restype = ctypes.c_uint64
-    lib.hsrle_compress_workspace_size.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
-    lib.hsrle_compress_workspace_size_codec.restype = ctypes.c_uint64
-    lib.hsrle_compress_workspace_size_codec.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32]
     general = lib.hsrle_compress_workspace_size(frame, 4096)
     assert lib.hsrle_compress_workspace_size_codec(cid("rle8_packed_multi"), frame, 4096) == general
     assert lib.hsrle_compress_workspace_size_codec(cid("rle8_single"), frame, 4096) == general          # round 6: position-parallel, no split regions
@@ -147,9 +148,6 @@ def test_decode_ring_rule(lib):
     products need 64 bits too."""
     from hsrle_testlib import CODECS
 
-    lib.hsrle_decode_ring.restype = ctypes.c_int
-    lib.hsrle_decode_ring.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64]
-    lib.hsrle_experiments_enabled.restype = ctypes.c_int
     assert not lib.hsrle_experiments_enabled() or not os.environ.get("HSRLE_DEC_RING"), "an experiments build with a forced ring does not follow the rule"
     for cid, c in enumerate(CODECS):
         T = 250 if c.S <= 2 else 215 if c.S <= 4 else 0
@@ -170,5 +168,4 @@ def test_decode_ring_rule(lib):
 def test_codec_table_matches_tests_table(lib):
     from hsrle_testlib import CODECS
 
-    lib.hsrle_codec_name.restype = ctypes.c_char_p
     assert [lib.hsrle_codec_name(i).decode() for i in range(110)] == [c.key for c in CODECS]

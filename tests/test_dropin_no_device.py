@@ -9,6 +9,8 @@ import random
 
 import pytest
 
+import hsrle
+
 from hsrle_testlib import CODEC_BY_KEY, mixed_runs
 
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "hypersonic-rle-kit_amd", "libhsrle_hip.so")
@@ -24,20 +26,7 @@ class DecompressInfo(ctypes.Structure):
 
 @pytest.fixture(scope="module")
 def lib():
-    L = ctypes.CDLL(LIB)                                               # (a missing library is a failed build: an error, not a skip)
-    p, u32 = ctypes.c_void_p, ctypes.c_uint32
-    for name in ("rle8_multi_compress", "rle8_decompress", "rle8m_decompress", "rle8_low_entropy_compress", "rle8_low_entropy_decompress"):
-        getattr(L, name).restype, getattr(L, name).argtypes = u32, [p, u32, p, u32]
-    L.rle8m_compress.restype, L.rle8m_compress.argtypes = u32, [u32, p, u32, p, u32]
-    L.rle8_low_entropy_get_compress_info.restype, L.rle8_low_entropy_get_compress_info.argtypes = ctypes.c_bool, [p, u32, p]
-    L.rle8_low_entropy_compress_with_info.restype, L.rle8_low_entropy_compress_with_info.argtypes = u32, [p, u32, p, p, u32]
-    L.rle8_low_entropy_decompress_with_info.restype, L.rle8_low_entropy_decompress_with_info.argtypes = u32, [p, p, p, p, u32]
-    L.rle8_low_entropy_read_decompress_info.restype, L.rle8_low_entropy_read_decompress_info.argtypes = u32, [p, u32, p]
-    L.hsrle_device_count.restype = ctypes.c_int
-    for name in ("rle_compress_bounds", "rle8_low_entropy_compress_bounds"):
-        getattr(L, name).restype, getattr(L, name).argtypes = u32, [u32]
-    L.rle8m_compress_bounds.restype, L.rle8m_compress_bounds.argtypes = u32, [u32, u32]
-    return L
+    return hsrle.declare(ctypes.CDLL(LIB))                            # (a missing library is a failed build: an error, not a skip)
 
 
 def _check(fn, args, pointers, succeeds):

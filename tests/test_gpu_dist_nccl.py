@@ -62,10 +62,6 @@ for name, kind in (("runs", hsrle.SYNTH_RUNS), ("noise", None)):
     # an error is an error code on every rank, never a hang): root without room, shard without room, a header that lies
     import ctypes
     L = hsrle.lib(); comm = hd.c_comm(); stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    L.hsrle_gather_container_rccl.restype = ctypes.c_int
-    L.hsrle_gather_container_rccl.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
-    L.hsrle_scatter_container_rccl.restype = ctypes.c_int
-    L.hsrle_scatter_container_rccl.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
     small = torch.empty(1024, dtype=torch.uint8, device=dev); total = ctypes.c_uint64(0)
     rc = L.hsrle_gather_container_rccl(comm, 0, ctypes.c_void_p(container.data_ptr()), container.numel(), size, ctypes.c_void_p(small.data_ptr()), small.numel(), ctypes.byref(total), stream)
     assert rc == 2 and total.value == full.numel(), ("gather into a root without room", rc)            # HSRLE_ERR_CAPACITY, and the size it needs

@@ -34,7 +34,6 @@ def hs():
 def _six_calls(hs, oracle, data, below_bound=False):
     """low-entropy, rle8m (7 sections), 8 bit Packed: compress == the oracle's stream, decompress of it == data"""
     lib = hs.lib()
-    lib.rle8_low_entropy_compress_bounds.restype = ctypes.c_uint32
     n = len(data)
     packed = CODEC_BY_KEY["rle8_packed_multi"]
     cases = (("rle8_low_entropy_compress", "rle8_low_entropy_decompress", lib.rle8_low_entropy_compress_bounds(ctypes.c_uint32(n)), oracle.low_entropy_compress(0, data)),
@@ -100,7 +99,7 @@ def test_staging_buffers_reused_across_families_and_sizes(hs, oracle):
 
     # the split-phase helpers on the same buffers: statistics, header, body == the oracle's whole stream; header reader + body decode == the input
     data = inverted
-    lib = helpers._bind(hs.lib())
+    lib = hs.lib()
     want = oracle.low_entropy_compress(0, data)
     info = helpers.CompressInfo()
     assert lib.rle8_low_entropy_get_compress_info(data, len(data), ctypes.byref(info))

@@ -109,11 +109,6 @@ PACKET_LIST = 1          # include/hsrle.h: HSRLE_SPLIT_PACKET_LIST
 def prologue_walk(L, info_type, container, out, stream=None):
     """{case: status} of the argument errors, each case with every LATER error present too, so that the status names the check that comes first.
     container / out: any two non-null device addresses -- no call gets as far as a launch."""
-    vp, u32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
-    L.hsrle_decompress_blocks_dev_async.restype = L.hsrle_decompress_dev_async.restype = L.hsrle_decompress_split_dev_async.restype = ctypes.c_int
-    L.hsrle_decompress_blocks_dev_async.argtypes = [vp, vp, u32, u32, vp, u64, vp, vp]
-    L.hsrle_decompress_dev_async.argtypes = [vp, vp, vp, u64, vp, vp]
-    L.hsrle_decompress_split_dev_async.argtypes = [vp, vp, u32, u32, vp, u64, vp, vp, u64, u32, vp]
     U = BLOCK * (BLOCKS - 1) + 100
 
     def info(codec=1, block=BLOCK, count=BLOCKS):

@@ -151,10 +151,7 @@ def check_host_names(hs, oracle, fixtures):
     lib = hs.lib()
     getters = []
     for name in ("rle8_low_entropy_get_compress_info", "rle8_low_entropy_get_compress_info_only_max_frequency"):
-        g = getattr(lib, name)
-        g.restype = ctypes.c_bool
-        g.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(CompressInfo)]
-        getters.append(g)
+        getters.append(getattr(lib, name))
     bad = []
     for f in fixtures:
         n = f.data.size
@@ -268,8 +265,6 @@ def test_capacity_and_argument_rule(hs):
         assert call.run(variant) == hs.ERR_ARGUMENT and untouched(call)
     f = hs.lib().hsrle_low_entropy_compress_dev_async
     vp = ctypes.c_void_p
-    f.restype = ctypes.c_int
-    f.argtypes = [vp, ctypes.c_uint32, ctypes.c_int, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp]
     src, ws, status = call.src.data_ptr(), call.ws.data_ptr(), call.words[1:2].data_ptr()
     args = lambda src, size, at, status: (vp(src), size, 0, vp(call.dst.data_ptr()), call.cap, vp(at), call.ws.numel() - (at - ws), vp(status), vp(torch.cuda.current_stream().cuda_stream))
     assert f(*args(None, n, ws, status)) == hs.ERR_ARGUMENT and untouched(call)              # a null input

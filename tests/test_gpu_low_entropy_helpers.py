@@ -36,6 +36,7 @@ def hs():
 
 
 def _bind(lib):
+    """the compiled reference's functions (the library's own are declared by the package)"""
     u8p, u32 = ctypes.c_char_p, ctypes.c_uint32
     for name in ("rle8_low_entropy_get_compress_info", "rle8_low_entropy_get_compress_info_only_max_frequency"):
         f = getattr(lib, name)
@@ -86,7 +87,7 @@ def _inputs():
 
 
 def test_the_whole_stream_is_its_helpers_in_a_row(hs, oracle):
-    lib = _bind(hs.lib())
+    lib = hs.lib()
     n = 0
     for data in _inputs():
         for only_max, getter in ((0, "rle8_low_entropy_get_compress_info"), (1, "rle8_low_entropy_get_compress_info_only_max_frequency")):
@@ -121,7 +122,7 @@ def test_the_whole_stream_is_its_helpers_in_a_row(hs, oracle):
 def test_helpers_against_the_compiled_reference(hs, reference):
     """Same arguments into oracle/_ref/libhsrle_ref.so (the reference's own code): structs and bodies must be identical -- also for the Short bodies and for
     tables nobody's statistics produced (every symbol flagged, odd code orders)."""
-    lib, ref = _bind(hs.lib()), _bind(reference.lib)
+    lib, ref = hs.lib(), _bind(reference.lib)
     rng = random.Random(77)
     n = 0
     for data in _inputs():

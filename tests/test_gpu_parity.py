@@ -213,7 +213,6 @@ def test_rle8m_decode_matches_the_oracle(hs, oracle):
 
     rng = random.Random(77)
     lib = hs.lib()
-    lib.rle8m_opencl_init.restype = ctypes.c_bool
     assert lib.rle8m_opencl_init(ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0))
     cases = [(mixed_runs(rng, 200000, alphabet=3), 64), (mixed_runs(rng, 70001, alphabet=256), 7), (single_symbol_mix(rng, 9000), 1),
              (bytes([5]) * 100000 + mixed_runs(rng, 3000), 16), (mixed_runs(rng, 333), 3), (bytes(range(256)) * 40 + b"\x00" * 5000, 33),
@@ -335,8 +334,6 @@ def test_low_entropy_unsectioned_forms_match_the_oracle(hs, oracle):
     bound, and both decoders read the oracle's streams; sizes around the encoders' 256-byte tail rule and runs around 32 / 255 included."""
     rng = random.Random(812)
     lib = hs.lib()
-    lib.rle8_low_entropy_compress_bounds.restype = ctypes.c_uint32
-    lib.rle8_low_entropy_decompressed_size.restype = ctypes.c_uint32
     inputs = [mixed_runs(rng, 200000, alphabet=3), single_symbol_mix(rng, 9000), bytes([5]) * 100000 + mixed_runs(rng, 3000), mixed_runs(rng, 333),
               bytes(range(256)) * 40 + b"\x00" * 5000, b"\x00" * 70000, b"\x07", b"ab" * 2000 + b"a" * 4000, bytes(rng.randrange(256) for _ in range(5000)),
               mixed_runs(rng, 1 << 20, alphabet=4),

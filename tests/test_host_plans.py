@@ -42,3 +42,18 @@ def test_codec_free_plans_are_the_recorded_ones():
     assert len(want["hsrle_rle8m_compress_workspace_size"]) == len(dump_host_plans.SIZES32) * len(want["sections"])
     for fn, values in want.items():
         assert got[fn] == values, fn
+
+
+def test_stream_codec_plans_are_the_recorded_ones():
+    """tests/golden/host_plans_stream.json: the stream codecs' workspace sizes, capacities and bounds (rle8_sh, rle8_mmtf128, the four mmtf transforms, the
+    rle8_sh block container), written by `dump_host_plans.py --stream` from the build before their plans took the shared round-up of csrc/hsrle_capi_host.h"""
+    import dump_host_plans
+
+    with open(os.path.join(REPO, "tests", "golden", "host_plans_stream.json")) as f:
+        want = json.load(f)
+    got = dump_host_plans.dump_stream(dump_host_plans.load())
+    assert list(got) == list(want)
+    assert want["sizes"] == [1, 15, 16, 4096, (1 << 20) + 128, 1 << 30, (1 << 30) + 1] and want["blocks"] == [0, 128, 4096, 65536, 1 << 20, 192]
+    assert len(want["hsrle_rle8_sh_blocks_bound"]) == len(want["sizes"]) * len(want["blocks"])
+    for fn, values in want.items():
+        assert got[fn] == values, fn

@@ -7,6 +7,8 @@ import random
 
 import pytest
 
+import hsrle
+
 from hsrle_testlib import Reference
 
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "hypersonic-rle-kit_amd", "libhsrle_hip.so")
@@ -21,6 +23,7 @@ class DecompressInfo(ctypes.Structure):
 
 
 def _bind(lib):
+    """the compiled reference's two functions (the library's own come from hsrle.declare)"""
     lib.rle8_low_entropy_write_compress_info.restype = ctypes.c_uint32
     lib.rle8_low_entropy_write_compress_info.argtypes = [ctypes.POINTER(CompressInfo), ctypes.c_char_p, ctypes.c_uint32]
     lib.rle8_low_entropy_read_decompress_info.restype = ctypes.c_uint32
@@ -32,7 +35,7 @@ def _bind(lib):
 def lib():
     if not os.path.exists(LIB):
         pytest.skip("libhsrle_hip.so not built")
-    return _bind(ctypes.CDLL(LIB))
+    return hsrle.declare(ctypes.CDLL(LIB))
 
 
 def _random_info(rng, count):

@@ -6,6 +6,8 @@ import os
 
 import pytest
 
+import hsrle
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(REPO, "hypersonic-rle-kit_amd", "libhsrle_hip.so")
 
@@ -27,15 +29,7 @@ def lib():
         import subprocess
 
         subprocess.check_call(["make", "-s", "-j8", "-C", os.path.join(REPO, "hypersonic-rle-kit_amd")])
-    L = ctypes.CDLL(LIB)
-    vp, u32, u64, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
-    L.hsrle_codec_name.restype = ctypes.c_char_p
-    L.hsrle_codec_name.argtypes = [ci]
-    L.rle_compress_bounds.restype = u32
-    L.rle_compress_bounds.argtypes = [u32]
-    L.hsrle_compress_mono_dev_enqueue.restype = ci
-    L.hsrle_compress_mono_dev_enqueue.argtypes = [ci, vp, u32, vp, u64, vp, u64, vp, vp, vp]
-    return L
+    return hsrle.declare(ctypes.CDLL(LIB))
 
 
 def codec_names(lib):

@@ -6,6 +6,8 @@ import os
 
 import pytest
 
+import hsrle
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(REPO, "hypersonic-rle-kit_amd", "libhsrle_hip.so")
 
@@ -22,22 +24,7 @@ def lib():
         import subprocess
 
         subprocess.check_call(["make", "-s", "-j8", "-C", os.path.join(REPO, "hypersonic-rle-kit_amd")])
-    L = ctypes.CDLL(LIB)
-    vp, u32, u64, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
-    for nm in REFERENCE_NAMES[:2]:
-        getattr(L, nm).restype = u32
-        getattr(L, nm).argtypes = [u32]
-    for nm in REFERENCE_NAMES[2:]:
-        getattr(L, nm).restype = u32
-        getattr(L, nm).argtypes = [vp, u32, vp, u32]
-    L.hsrle_rle8_mmtf128_workspace_size.restype = u64
-    L.hsrle_rle8_mmtf128_workspace_size.argtypes = [ci, u64]
-    L.hsrle_rle8_mmtf128_compress_dev_async.restype = ci
-    L.hsrle_rle8_mmtf128_compress_dev_async.argtypes = [vp, u64, vp, u64, vp, vp, vp, u64, vp]
-    L.hsrle_rle8_mmtf128_decompress_dev_async.restype = ci
-    L.hsrle_rle8_mmtf128_decompress_dev_async.argtypes = [vp, u64, vp, u64, vp, vp, u64, vp]
-    L.hsrle_rle8_mmtf_tuning.restype = None
-    L.hsrle_rle8_mmtf_tuning.argtypes = [u32]
+    L = hsrle.declare(ctypes.CDLL(LIB))
     L.hsrle_rle8_mmtf_tuning(0)
     return L
 

@@ -7,6 +7,8 @@ import struct
 
 import pytest
 
+import hsrle
+
 import rle8_sh_blocks_testlib as B
 import rle8_sh_testlib as T
 
@@ -20,14 +22,7 @@ OK, ERR_ARGUMENT, ERR_CAPACITY, ERR_FORMAT = 0, 1, 2, 3
 DEFAULT_IN_FLIGHT = {128: 8192, 1024: 8192, 4096: 8192, 16384: 2048, 65536: 512, 1 << 20: 256}     # 32 MiB a group, 256 .. 8192 blocks
 
 
-class Info(ctypes.Structure):
-    _fields_ = [("uncompressedSize", ctypes.c_uint64), ("blockSize", ctypes.c_uint32), ("blockCount", ctypes.c_uint32), ("payloadSize", ctypes.c_uint64),
-                ("totalSize", ctypes.c_uint64)]
-
-
-class KitInfo(ctypes.Structure):
-    _fields_ = [("version", ctypes.c_uint32), ("codec", ctypes.c_uint32), ("uncompressedSize", ctypes.c_uint64), ("blockSize", ctypes.c_uint32),
-                ("blockCount", ctypes.c_uint32), ("payloadSize", ctypes.c_uint64), ("totalSize", ctypes.c_uint64)]
+Info, KitInfo = hsrle.Rle8ShBlocksInfo, hsrle.ContainerInfo
 
 
 @pytest.fixture(scope="module")
@@ -36,30 +31,9 @@ def lib():
         import subprocess
 
         subprocess.check_call(["make", "-s", "-j8", "-C", os.path.join(REPO, "hypersonic-rle-kit_amd")])
-    L = ctypes.CDLL(LIB)
+    L = hsrle.declare(ctypes.CDLL(LIB))
     for nm in NAMES:
         assert hasattr(L, nm), nm
-    vp, u32, u64, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
-    L.hsrle_rle8_sh_blocks_bound.restype = u64
-    L.hsrle_rle8_sh_blocks_bound.argtypes = [u64, u32]
-    L.hsrle_rle8_sh_blocks_workspace_size.restype = u64
-    L.hsrle_rle8_sh_blocks_workspace_size.argtypes = [ci, u64, u32]
-    L.hsrle_rle8_sh_workspace_size.restype = u64
-    L.hsrle_rle8_sh_workspace_size.argtypes = [ci, u64]
-    L.hsrle_rle8_sh_blocks_info_host.restype = ci
-    L.hsrle_rle8_sh_blocks_info_host.argtypes = [vp, u64, ctypes.POINTER(Info)]
-    L.hsrle_container_info_host.restype = ci
-    L.hsrle_container_info_host.argtypes = [vp, u64, ctypes.POINTER(KitInfo)]
-    L.hsrle_rle8_sh_compress_blocks_dev_async.restype = ci
-    L.hsrle_rle8_sh_compress_blocks_dev_async.argtypes = [vp, u64, u32, vp, u64, vp, vp, vp, u64, vp]
-    L.hsrle_rle8_sh_decompress_blocks_dev_async.restype = ci
-    L.hsrle_rle8_sh_decompress_blocks_dev_async.argtypes = [vp, ctypes.POINTER(Info), u32, u32, vp, u64, vp, vp, u64, vp]
-    L.hsrle_rle8_sh_compress_blocks_host.restype = ci
-    L.hsrle_rle8_sh_compress_blocks_host.argtypes = [vp, u64, u32, vp, u64, ctypes.POINTER(u64)]
-    L.hsrle_rle8_sh_decompress_blocks_host.restype = ci
-    L.hsrle_rle8_sh_decompress_blocks_host.argtypes = [vp, u64, vp, u64, ctypes.POINTER(u64)]
-    L.hsrle_rle8_sh_blocks_tuning.restype = None
-    L.hsrle_rle8_sh_blocks_tuning.argtypes = [u32]
     L.hsrle_rle8_sh_blocks_tuning(0)
     yield L
     L.hsrle_rle8_sh_blocks_tuning(0)

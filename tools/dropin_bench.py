@@ -24,8 +24,6 @@ for key, kind, size in (("rle8_packed_multi", 0, 1 << 30), ("rle8_packed_multi",
     stream = ora.compress(codec, data.tobytes())
     out = ctypes.create_string_buffer(size + 256)
     f = getattr(hsrle.lib(), codec.dname)
-    f.restype = ctypes.c_uint32
-    f.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32]
     best = None
     for _ in range(4):
         t0 = time.perf_counter()

@@ -2,6 +2,7 @@
 """What the device-free planning entry points of libhsrle_hip.so return, for every codec over a fixed grid: the host side's behaviour as data.
 
   python tools/dump_host_plans.py [out.json]        (HSRLE_LIB=<path> picks another build of the library)
+  python tools/dump_host_plans.py --stream [out.json]   the stream codecs' plans alone (tests/golden/host_plans_stream.json)
 
 tests/golden/host_plans.json is this tool's output for the build the codec traits table (csrc/hsrle_codecs.h) replaced;
 its "codec_free" rows (the low-entropy and rle8m workspaces, which take no codec id) were written from the build before
@@ -29,21 +30,10 @@ def compressed_sizes(U):
 
 
 def load(path=LIB):
-    L = ctypes.CDLL(path)
-    u32, u64, ci = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
-    L.hsrle_codec_name.restype = ctypes.c_char_p
-    L.hsrle_codec_name.argtypes = [ci]
-    L.hsrle_encode_path.restype = ci
-    L.hsrle_encode_path.argtypes = [ci, u64, u32]
-    for name, args in (("hsrle_compress_workspace_size_codec", [ci, u64, u32]), ("hsrle_compress_mono_workspace_size", [ci, u32]),
-                       ("hsrle_decompress_mono_workspace_size", [ci, u32, u32]), ("hsrle_mono_index_size", [ci, u32, u32, u32]),
-                       ("hsrle_mono_index_workspace_size", [ci, u32, u32, u32])):
-        getattr(L, name).restype = u64
-        getattr(L, name).argtypes = args
-    for name, args in (("hsrle_low_entropy_workspace_size", [u32]), ("hsrle_low_entropy_decompress_workspace_size", [u64]), ("hsrle_rle8m_compress_workspace_size", [u32, u32])):
-        getattr(L, name).restype = u64
-        getattr(L, name).argtypes = args
-    return L
+    sys.path.insert(0, os.path.join(REPO, "hypersonic-rle-kit_amd", "python"))
+    import hsrle                                                         # (the signature table; importing it needs neither torch nor a device)
+
+    return hsrle.declare(ctypes.CDLL(path))
 
 
 def dump(L):
@@ -84,12 +74,40 @@ def dump_codec_free(L):
     }
 
 
+STREAM_SIZES = [1, 15, 16, 4096, (1 << 20) + 128, 1 << 30, (1 << 30) + 1]
+STREAM_BLOCKS = [0, 128, 4096, 65536, 1 << 20, 192]   # 0: the default; 192: no multiple of 128, refused
+TRANSFORMS = ["mmtf128", "mmtf256", "bitmmtf8", "bitmmtf16"]
+
+
+def dump_stream(L):
+    """the plans of the stream codecs (rle8_sh, rle8_mmtf128, the mmtf transforms, the rle8_sh block container) over STREAM_SIZES: rows with a direction
+    are {"compress": ..., "decompress": ...}, the transforms' one row each, the container's rows sizes outermost x STREAM_BLOCKS.  Tunings at their defaults."""
+    both = lambda call: {"compress": call(0), "decompress": call(1)}   # noqa: E731
+    return {
+        "sizes": STREAM_SIZES,
+        "blocks": STREAM_BLOCKS,
+        "hsrle_rle8_sh_workspace_size": both(lambda d: [L.hsrle_rle8_sh_workspace_size(d, U) for U in STREAM_SIZES]),
+        "hsrle_rle8_sh_capacity": [L.hsrle_rle8_sh_capacity(U) for U in STREAM_SIZES],
+        "rle8_sh_bounds": [L.rle8_sh_bounds(U) for U in STREAM_SIZES],
+        "hsrle_rle8_mmtf128_workspace_size": both(lambda d: [L.hsrle_rle8_mmtf128_workspace_size(d, U) for U in STREAM_SIZES]),
+        "rle8_mmtf128_compress_bounds": [L.rle8_mmtf128_compress_bounds(U) for U in STREAM_SIZES],
+        "hsrle_mmtf_workspace_size": {nm: [L.hsrle_mmtf_workspace_size(t, U) for U in STREAM_SIZES] for t, nm in enumerate(TRANSFORMS)},
+        "hsrle_rle8_sh_blocks_bound": [L.hsrle_rle8_sh_blocks_bound(U, B) for U in STREAM_SIZES for B in STREAM_BLOCKS],
+        "hsrle_rle8_sh_blocks_workspace_size": both(lambda d: [L.hsrle_rle8_sh_blocks_workspace_size(d, U, B) for U in STREAM_SIZES for B in STREAM_BLOCKS]),
+    }
+
+
 def expand(results):
     """{entry point: {codec name: values}}"""
     return {fn: {nm: r["vectors"][k] for nm, k in r["codec"].items()} for fn, r in results.items()}
 
 
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["--stream"]:
+        text = "{\n%s\n}" % ",\n".join(' "%s": %s' % (k, json.dumps(v, separators=(",", ":"))) for k, v in dump_stream(load()).items())
+        with (open(sys.argv[2], "w") if len(sys.argv) > 2 else sys.stdout) as f:
+            f.write(text + "\n")
+        sys.exit(0)
     d = dump(load())
     # one line per entry point and part: short enough to read, few enough lines to review
     rows = ['  "%s": {"vectors": %s,\n    "codec": %s}' % (fn, json.dumps(r["vectors"], separators=(",", ":")), json.dumps(r["codec"], separators=(",", ":"))) for fn, r in d["results"].items()]

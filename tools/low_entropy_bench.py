@@ -8,12 +8,6 @@ import torch, hsrle
 from hsrle_testlib import Oracle, Reference, REF_SO
 size = (int(sys.argv[1]) if len(sys.argv) > 1 else 1024) << 20
 L = hsrle.lib()
-L.hsrle_low_entropy_workspace_size.restype = ctypes.c_uint64
-L.hsrle_low_entropy_decompress_workspace_size.restype = ctypes.c_uint64
-L.hsrle_low_entropy_decompress_workspace_size.argtypes = [ctypes.c_uint64]
-vp, u32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
-L.hsrle_low_entropy_compress_dev_async.argtypes = [vp, u32, ctypes.c_int, vp, u64, vp, u64, vp, vp]
-L.hsrle_low_entropy_decompress_dev.argtypes = [vp, u64, vp, u64, vp, u64, ctypes.POINTER(u32), vp]
 cpu = Reference() if os.path.exists(REF_SO) else Oracle()
 names = ("rle8_low_entropy", "rle8_low_entropy_short", "rle8_low_entropy_only_max_frequency", "rle8_low_entropy_short_only_max_frequency")
 print("library build", hsrle.build_id(), "| %d MiB, device resident | CPU: %s, one core, first 64 MiB" % (size >> 20, "compiled reference" if isinstance(cpu, Reference) else "oracle"))
