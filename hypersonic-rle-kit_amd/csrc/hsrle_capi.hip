@@ -35,6 +35,7 @@ using namespace hsrle;
 #include "hsrle_capi_mmtf.h"                // the mmtf / bitmmtf transforms and rle8_mmtf128: plans, their C ABI, their host-pointer functions
 #include "hsrle_capi_sh.h"                  // rle8_sh, both directions: plans, C ABI, host-pointer functions
 #include "hsrle_capi_shb.h"                 // the rle8_sh block container: many independent rle8_sh streams per call
+#include "hsrle_capi_mmtfb.h"               // the rle8_mmtf128 block container: the same container of rle8_mmtf128 streams
 
 extern "C" {
 

@@ -20,9 +20,9 @@ static bool shb_valid_block(uint32_t B) { return B >= kShbBlockMin && B <= kShbB
 static uint64_t shb_block_count(uint64_t size, uint32_t B) { return (size + B - 1u) / B; }
 static uint64_t shb_table_end(uint64_t blocks) { return kShbHeaderBytes + 8ull * (blocks + 1u); }
 
-static uint32_t shb_in_flight(uint32_t B)
+// `t`: the family's tuning value (0 = the default)
+static uint32_t shb_in_flight(uint32_t t, uint32_t B)
 {
-  const uint32_t t = g_shbInFlight.load();
   if (t != 0u) return t;
   const uint64_t d = kShbGroupBytes / B;
   return d > kShbInFlightMax ? kShbInFlightMax : (d < kShbInFlightMin ? kShbInFlightMin : (uint32_t)d);
@@ -34,7 +34,7 @@ static bool rle8shb_plan(uint64_t size, uint32_t B, uint64_t blocks, ShbPlan &p)
   const uint64_t all = size == 0u || !shb_valid_block(B) ? 0u : shb_block_count(size, B);
   if (all == 0u || all > 0xFFFFFFFFull || blocks == 0u || blocks > all || !rle8sh_enc_plan(B, p.enc) || !rle8sh_plan(B, p.dec))
     return false;
-  const uint32_t fly = shb_in_flight(B);
+  const uint32_t fly = shb_in_flight(g_shbInFlight.load(), B);
   p.size = size;
   p.blockSize = B;
   p.blockCount = (uint32_t)all;
@@ -50,13 +50,14 @@ static uint64_t rle8shb_bound(uint64_t size, uint32_t B)
   return shb_table_end(blocks) + (blocks - 1u) * rle8sh_capacity(B) + rle8sh_capacity(size - (blocks - 1u) * B) + kShbPadBytes;
 }
 
-static int shb_check_info(const uint8_t h[64], uint64_t containerSize, hsrle_rle8_sh_blocks_info_t *info)
+// (both stream-block containers: the same header lines under the family's own magic)
+static int shb_check_info(const char magic[8], const uint8_t h[64], uint64_t containerSize, hsrle_rle8_sh_blocks_info_t *info)
 {
   uint32_t version, reserved, B, blocks;
   uint64_t size, payload, total;
   memcpy(&version, h + 8, 4); memcpy(&reserved, h + 12, 4); memcpy(&size, h + 16, 8); memcpy(&B, h + 24, 4); memcpy(&blocks, h + 28, 4);
   memcpy(&payload, h + 32, 8); memcpy(&total, h + 40, 8);
-  if (memcmp(h, kShbMagic, 8) != 0 || version != 1u || reserved != 0u)
+  if (memcmp(h, magic, 8) != 0 || version != 1u || reserved != 0u)
     return HSRLE_ERR_FORMAT;
   for (int k = 48; k < 64; k++)
     if (h[k] != 0u) return HSRLE_ERR_FORMAT;
@@ -95,7 +96,7 @@ uint64_t hsrle_rle8_sh_blocks_workspace_size(int decode, uint64_t inSize, uint32
 int hsrle_rle8_sh_blocks_info_host(const void *pContainer, uint64_t containerSize, hsrle_rle8_sh_blocks_info_t *pInfo)
 {
   if (!pContainer || !pInfo || containerSize < kShbHeaderBytes) return HSRLE_ERR_ARGUMENT;
-  return shb_check_info((const uint8_t *)pContainer, containerSize, pInfo);
+  return shb_check_info(kShbMagic, (const uint8_t *)pContainer, containerSize, pInfo);
 }
 
 int hsrle_rle8_sh_blocks_info_dev(const void *dContainer, uint64_t containerSize, hsrle_rle8_sh_blocks_info_t *pInfo, void *stream)
@@ -105,7 +106,7 @@ int hsrle_rle8_sh_blocks_info_dev(const void *dContainer, uint64_t containerSize
   uint8_t h[64];
   if (hipMemcpyAsync(h, dContainer, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess || hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
     return HSRLE_ERR_DEVICE;
-  return shb_check_info(h, containerSize, pInfo);
+  return shb_check_info(kShbMagic, h, containerSize, pInfo);
 }
 
 int hsrle_rle8_sh_compress_blocks_dev_async(const void *dIn, uint64_t inSize, uint32_t blockSize, void *dOut, uint64_t outCapacity, uint64_t *dOutSize, uint32_t *dStatus,

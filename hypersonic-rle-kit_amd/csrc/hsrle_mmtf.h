@@ -31,4 +31,20 @@ struct Rle8MmtfPlan
 hipError_t rle8mmtf_compress_enqueue(const Rle8MmtfPlan &p, const uint8_t *dIn, uint8_t *dOut, uint32_t outCap, uint32_t *dOutSize, uint32_t *dStatus, uint8_t *ws, hipStream_t st);
 hipError_t rle8mmtf_decompress_enqueue(const Rle8MmtfPlan &p, const uint8_t *dStream, uint32_t streamCap, uint8_t *dOut, uint32_t *dStatus, uint8_t *ws, hipStream_t st);
 
+// The blocked form (hsrle_capi_mmtfb.h plans, inst_rle8mmtfb.hip launches, kernels: hsrle_rle8mmtfb.hip.h).  Workspace, from its 256-byte aligned start:
+// 256 bytes of words for the whole call, then `inFlight` SLOTS: control words, the block's rank buffer, then -- encode: the span summaries and the span
+// results of a block; decode: its packet records.
+struct MfbPlan
+{
+  uint64_t size = 0;                // uncompressed bytes of the whole container
+  uint32_t blockSize = 0, blockCount = 0;
+  uint32_t inFlight = 0;            // blocks per group: min(blocks of the call, blocks in flight)
+  uint32_t SP = 0, maxRec = 0;      // encode: rows per span; decode: records a slot can hold
+  uint64_t offRanks = 0, offA = 0, offB = 0;   // inside a slot; A: summaries / records, B: results
+  uint64_t encSlot = 0, decSlot = 0;
+};
+hipError_t rle8mmtfb_compress_enqueue(const MfbPlan &p, const uint8_t *dIn, uint8_t *dOut, uint64_t outCap, uint64_t *dOutSize, uint32_t *dStatus, uint8_t *ws, hipStream_t st);
+hipError_t rle8mmtfb_decompress_enqueue(const MfbPlan &p, const uint8_t *dContainer, uint64_t payloadSize, uint32_t firstBlock, uint32_t blockCount, uint8_t *dOut,
+                                        uint32_t *dStatus, uint8_t *ws, hipStream_t st);
+
 }   // namespace hsrle

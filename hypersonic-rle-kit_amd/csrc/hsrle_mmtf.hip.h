@@ -143,27 +143,12 @@ struct MmtfArgs
   uint32_t size, rows, R, S;   // rows = size / W, R rows per segment, S = ceil(rows / R) >= 1
 };
 
-// Passes A (FINAL = false: segments 0 .. S - 2, from identity, leaves the state) and C (FINAL = true: from the table, writes the output).
+// The row loop of a lane: `segRows` rows of column `col` from `src` through the list L, in tiles of 16 rows that reach the lanes through `tile` (the 16 rows
+// of the lane's segment in LDS); FINAL: the ranks / symbols go to `dst` the same way.  `trips` is the same for every lane of the workgroup (the barriers
+// are uniform); a lane without rows (segRows = 0) only keeps them.  K (encode, !FINAL): the number of distinct symbols so far.
 template <int W, bool DEC, bool FINAL>
-__global__ __launch_bounds__(64) void k_mmtf_rows(MmtfArgs a)
+__device__ __forceinline__ void d_mmtf_rows(MmtfList &L, uint32_t &K, const uint8_t *src, uint8_t *dst, uint32_t segRows, uint32_t trips, uint32_t col, uint8_t *tile)
 {
-  __shared__ uint32_t sList[kMmtfGroupDwords];
-  __shared__ __attribute__((aligned(16))) uint8_t sTile[1024];
-  const uint32_t lane = threadIdx.x, g = blockIdx.x;
-  const uint32_t seg = (g * 64u + lane) / (uint32_t)W, col = lane % (uint32_t)W;
-  const uint32_t segs = FINAL ? a.S : a.S - 1u;
-  const bool valid = seg < segs;
-  const uint32_t firstRow = valid ? seg * a.R : 0u;
-  const uint32_t segRows = valid ? umin(a.R, a.rows - firstRow) : 0u;
-  MmtfList L;
-  L.lds = sList + lane;
-  uint32_t *slot = a.table + (uint64_t)g * kMmtfGroupDwords + lane;
-  if (FINAL && valid && seg != 0u) L.load(slot); else L.identity();
-  uint32_t K = 0;
-  uint8_t *tile = sTile + (lane / (uint32_t)W) * 16u * (uint32_t)W;   // this segment's 16 rows
-  const uint8_t *src = a.in + (uint64_t)firstRow * W;
-  uint8_t *dst = a.out + (uint64_t)firstRow * W;
-  const uint32_t trips = (a.R + 15u) / 16u;   // the same for every lane: the barriers below are uniform
   u32x4 next = { 0u, 0u, 0u, 0u };
   if (segRows >= 16u) next = ld128(src + col * 16u);
   for (uint32_t t = 0; t < trips; t++)
@@ -222,6 +207,27 @@ __global__ __launch_bounds__(64) void k_mmtf_rows(MmtfArgs a)
     else
       __syncthreads();
   }
+}
+
+// Passes A (FINAL = false: segments 0 .. S - 2, from identity, leaves the state) and C (FINAL = true: from the table, writes the output).
+template <int W, bool DEC, bool FINAL>
+__global__ __launch_bounds__(64) void k_mmtf_rows(MmtfArgs a)
+{
+  __shared__ uint32_t sList[kMmtfGroupDwords];
+  __shared__ __attribute__((aligned(16))) uint8_t sTile[1024];
+  const uint32_t lane = threadIdx.x, g = blockIdx.x;
+  const uint32_t seg = (g * 64u + lane) / (uint32_t)W, col = lane % (uint32_t)W;
+  const uint32_t segs = FINAL ? a.S : a.S - 1u;
+  const bool valid = seg < segs;
+  const uint32_t firstRow = valid ? seg * a.R : 0u;
+  const uint32_t segRows = valid ? umin(a.R, a.rows - firstRow) : 0u;
+  MmtfList L;
+  L.lds = sList + lane;
+  uint32_t *slot = a.table + (uint64_t)g * kMmtfGroupDwords + lane;
+  if (FINAL && valid && seg != 0u) L.load(slot); else L.identity();
+  uint32_t K = 0;
+  uint8_t *tile = sTile + (lane / (uint32_t)W) * 16u * (uint32_t)W;   // this segment's 16 rows
+  d_mmtf_rows<W, DEC, FINAL>(L, K, a.in + (uint64_t)firstRow * W, a.out + (uint64_t)firstRow * W, segRows, (a.R + 15u) / 16u, col, tile);
   if (!FINAL)
   {
     if (valid)

@@ -140,11 +140,10 @@ struct RmEncArgs
   uint32_t size, rows, SP, spans, outCap;
 };
 
-template <int UNUSED = 0>
-__global__ __launch_bounds__(256) void k_rm_classify(RmEncArgs a)
+// The passes are __device__ functions of one wave (d_rm_scan: of one workgroup): the kernels below call them for the one stream of a call, the kernels
+// of the blocked form (hsrle_rle8mmtfb.hip.h: a wave per block) for the stream of every block.
+__device__ __forceinline__ void d_rm_classify(const RmEncArgs &a, uint32_t span, uint32_t lane)
 {
-  const uint32_t lane = threadIdx.x & 63u, span = blockIdx.x * 4u + (threadIdx.x >> 6);
-  if (span >= a.spans) return;
   RmSpan s;
   rm_span_load(a.ranks, a.rows, a.SP, span, lane, s);
   const uint32_t ns = (uint32_t)__popcll(s.M);
@@ -165,12 +164,19 @@ __global__ __launch_bounds__(256) void k_rm_classify(RmEncArgs a)
 }
 
 template <int UNUSED = 0>
-__global__ __launch_bounds__(1024) void k_rm_scan(RmEncArgs a)
+__global__ __launch_bounds__(256) void k_rm_classify(RmEncArgs a)
 {
-  __shared__ uint32_t sA[kRmScanThreads], sB[kRmScanThreads];
-  __shared__ uint32_t sTotal;
-  const uint32_t t = threadIdx.x, N = a.spans, SP = a.SP;
-  const uint32_t per = (N + kRmScanThreads - 1u) / kRmScanThreads;
+  const uint32_t lane = threadIdx.x & 63u, span = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (span >= a.spans) return;
+  d_rm_classify(a, span, lane);
+}
+
+// A workgroup of T threads (sA, sB: T words of LDS each, sTotal: one): closes and places the packets; returns the offset behind the last packet.
+template <uint32_t T>
+__device__ __forceinline__ uint32_t d_rm_scan(const RmEncArgs &a, uint32_t t, uint32_t *sA, uint32_t *sB, uint32_t *sTotal)
+{
+  const uint32_t N = a.spans, SP = a.SP;
+  const uint32_t per = (N + T - 1u) / T;
   const uint64_t lo64 = (uint64_t)t * per;
   const uint32_t lo = (uint32_t)(lo64 < N ? lo64 : N), hi = (uint32_t)(lo64 + per < N ? lo64 + per : N);
   // suffix pass: the next packet start behind a span and the OR of the rows up to it.  First the run's summary ...
@@ -187,7 +193,7 @@ __global__ __launch_bounds__(1024) void k_rm_scan(RmEncArgs a)
   if (t == 0u)   // ... then what comes in from the right of every run
   {
     uint32_t n = a.rows, o = 0u;
-    for (uint32_t i = kRmScanThreads; i-- > 0u;)
+    for (uint32_t i = T; i-- > 0u;)
     {
       const uint32_t f = sA[i], g = sB[i];
       sA[i] = n;
@@ -225,7 +231,7 @@ __global__ __launch_bounds__(1024) void k_rm_scan(RmEncArgs a)
   if (t == 0u)
   {
     uint32_t base = 8u, prev = kRmNone;
-    for (uint32_t i = 0; i < kRmScanThreads; i++)
+    for (uint32_t i = 0; i < T; i++)
     {
       const uint32_t b = sA[i], l = sB[i];
       sA[i] = base;
@@ -233,7 +239,7 @@ __global__ __launch_bounds__(1024) void k_rm_scan(RmEncArgs a)
       base += b;
       if (l != kRmNone) prev = l;
     }
-    sTotal = base;
+    *sTotal = base;
   }
   __syncthreads();
   uint32_t base = sA[t], prev = sB[t];
@@ -247,33 +253,47 @@ __global__ __launch_bounds__(1024) void k_rm_scan(RmEncArgs a)
     base += b;
     if (a.sum[k].x & 0xFFu) prev = k;
   }
-  if (t == 0u)
+  return *sTotal;
+}
+
+// the chain's end: 0x06 0x00 without a row, 0x00 behind a last COPY, 0x00 0x00 behind a last RLE
+__device__ __forceinline__ uint32_t rm_chain_end(const RmEncArgs &a)
+{
+  const uint32_t R = a.rows;
+  return (R == 0u || rm_row_class(rm_ld_row(a.ranks, R - 1u)) != 0u) ? 2u : 1u;
+}
+// one lane: the header, the chain's end at `at` and the tail ranks behind it; the stream's size is at + end + the tail
+__device__ __forceinline__ void d_rm_close(const RmEncArgs &a, uint32_t at, uint32_t end)
+{
+  const uint32_t R = a.rows, tail = a.size - R * 16u;
+  st32(a.out, a.size);
+  st32(a.out + 4, at + end + tail);
+  a.out[at] = R == 0u ? (uint8_t)0x06 : (uint8_t)0;
+  if (end == 2u) a.out[at + 1u] = 0;
+  for (uint32_t i = 0; i < tail; i++) a.out[at + end + i] = a.ranks[(uint64_t)R * 16u + i];
+}
+
+template <int UNUSED = 0>
+__global__ __launch_bounds__(1024) void k_rm_scan(RmEncArgs a)
+{
+  __shared__ uint32_t sA[kRmScanThreads], sB[kRmScanThreads];
+  __shared__ uint32_t sTotal;
+  const uint32_t at = d_rm_scan<kRmScanThreads>(a, threadIdx.x, sA, sB, &sTotal);
+  if (threadIdx.x == 0u)
   {
-    // the chain's end and the tail: 0x06 0x00 without a row, 0x00 behind a last COPY, 0x00 0x00 behind a last RLE
-    const uint32_t R = a.rows, tail = a.size - R * 16u;
-    const bool lastRle = R != 0u && rm_row_class(rm_ld_row(a.ranks, R - 1u)) != 0u;
-    const uint32_t end = (R == 0u || lastRle) ? 2u : 1u;
-    const uint32_t at = sTotal, total = at + end + tail;
+    const uint32_t end = rm_chain_end(a), total = at + end + (a.size - a.rows * 16u);
     const bool fits = total <= a.outCap;
-    if (fits)
-    {
-      st32(a.out, a.size);
-      st32(a.out + 4, total);
-      a.out[at] = R == 0u ? (uint8_t)0x06 : (uint8_t)0;
-      if (end == 2u) a.out[at + 1u] = 0;
-      for (uint32_t i = 0; i < tail; i++) a.out[at + end + i] = a.ranks[(uint64_t)R * 16u + i];
-    }
+    if (fits) d_rm_close(a, at, end);
     a.ctrl[0] = fits ? 0u : 1u;
     *a.outSize = fits ? total : 0u;
     *a.status = fits ? kRmDone : kRmCapacity;
   }
 }
 
-template <int UNUSED = 0>
-__global__ __launch_bounds__(256) void k_rm_emit(RmEncArgs a)
+// Every store lies inside the packet it belongs to and is a whole byte, word or vector of it: nothing is read-modify-written, nothing lands behind the
+// stream.  The other rows of a 2 / 3 / 4 bit group come from a.ranks, below row a.rows.
+__device__ __forceinline__ void d_rm_emit(const RmEncArgs &a, uint32_t span, uint32_t lane)
 {
-  const uint32_t lane = threadIdx.x & 63u, span = blockIdx.x * 4u + (threadIdx.x >> 6);
-  if (span >= a.spans || a.ctrl[0] != 0u) return;
   RmSpan s;
   rm_span_load(a.ranks, a.rows, a.SP, span, lane, s);
   const uint4 r = a.res[span];
@@ -370,6 +390,14 @@ __global__ __launch_bounds__(256) void k_rm_emit(RmEncArgs a)
   }
 }
 
+template <int UNUSED = 0>
+__global__ __launch_bounds__(256) void k_rm_emit(RmEncArgs a)
+{
+  const uint32_t lane = threadIdx.x & 63u, span = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (span >= a.spans || a.ctrl[0] != 0u) return;
+  d_rm_emit(a, span, lane);
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // decode
 
@@ -392,12 +420,14 @@ __device__ __forceinline__ u32x4 rm_ld_stream(const uint8_t *stream, uint64_t at
   return v;
 }
 
-template <int UNUSED = 0>
-__global__ __launch_bounds__(64) void k_rm_walk(RmDecArgs a)
+constexpr uint32_t kRmWalkWindow = 1024u;
+
+// One wave that is a workgroup of its own (the window's refill is a barrier); sWin: kRmWalkWindow bytes of LDS, 16-byte aligned.  Reads nothing of the
+// stream at or behind a.streamCap; writes the records, a.ctrl[0 .. 2] and *a.status.
+__device__ __forceinline__ void d_rm_walk(const RmDecArgs &a, uint8_t *sWin, uint32_t lane)
 {
-  constexpr uint32_t kWin = 1024u, kStep = kWin - 16u, kNeed = 8u;   // a header is at most 5 bytes
-  __shared__ __attribute__((aligned(16))) uint8_t sWin[kWin];
-  const uint32_t lane = threadIdx.x, R = a.rows;
+  constexpr uint32_t kWin = kRmWalkWindow, kStep = kWin - 16u, kNeed = 8u;   // a header is at most 5 bytes
+  const uint32_t R = a.rows;
   uint32_t status = kRmDone, n = 0u, row = 0u;
   uint64_t pos = 8u;
   uint32_t S = 0u;
@@ -464,12 +494,16 @@ __global__ __launch_bounds__(64) void k_rm_walk(RmDecArgs a)
 }
 
 template <int UNUSED = 0>
-__global__ __launch_bounds__(256) void k_rm_expand(RmDecArgs a)
+__global__ __launch_bounds__(64) void k_rm_walk(RmDecArgs a)
 {
-  if (a.ctrl[0] != kRmDone) return;
-  const uint32_t lane = threadIdx.x & 63u, row0 = (blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u, R = a.rows;
-  if (blockIdx.x == 0u && threadIdx.x < a.size - R * 16u) a.ranks[(uint64_t)R * 16u + threadIdx.x] = a.stream[a.ctrl[2] + threadIdx.x];
-  if (row0 >= R) return;
+  __shared__ __attribute__((aligned(16))) uint8_t sWin[kRmWalkWindow];
+  d_rm_walk(a, sWin, threadIdx.x);
+}
+
+// a wave: rows row0 .. row0 + 63 (row0 < a.rows) into the rank buffer
+__device__ __forceinline__ void d_rm_expand(const RmDecArgs &a, uint32_t row0, uint32_t lane)
+{
+  const uint32_t R = a.rows;
   const uint32_t n = a.ctrl[1];
   // the packet of the span's first row (the records cover rows 0 .. R without a gap, record 0 starts at row 0) ...
   uint32_t lo = 0u, hi = n;
@@ -540,6 +574,22 @@ __global__ __launch_bounds__(256) void k_rm_expand(RmDecArgs a)
     }
   }
   *(u32x4 *)__builtin_assume_aligned(a.ranks + (uint64_t)row * 16u, 16) = v;
+}
+// the tail ranks behind the rows: lanes 0 .. 14
+__device__ __forceinline__ void d_rm_expand_tail(const RmDecArgs &a, uint32_t lane)
+{
+  const uint32_t R = a.rows;
+  if (lane < a.size - R * 16u) a.ranks[(uint64_t)R * 16u + lane] = a.stream[a.ctrl[2] + lane];
+}
+
+template <int UNUSED = 0>
+__global__ __launch_bounds__(256) void k_rm_expand(RmDecArgs a)
+{
+  if (a.ctrl[0] != kRmDone) return;
+  const uint32_t lane = threadIdx.x & 63u, row0 = (blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u;
+  if (blockIdx.x == 0u) d_rm_expand_tail(a, threadIdx.x);
+  if (row0 >= a.rows) return;
+  d_rm_expand(a, row0, lane);
 }
 
 }   // namespace hsrle

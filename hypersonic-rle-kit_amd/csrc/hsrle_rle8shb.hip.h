@@ -8,25 +8,26 @@
 // store the body byte by byte or as whole words INSIDE a record, 16 bytes only inside a raw COPY, and the bit stream is placed byte by byte.
 //
 // Blocks go through in GROUPS of `count` (the host loops and only enqueues); a block of the group owns slot `blockIdx.x` of the workspace.
-//   encode  k_shb_begin          the running payload size and the does-not-fit word: zero
+//   encode  k_blk_begin          the running payload size and the does-not-fit word: zero
 //           k_shb_decide_code    per block: decide, then the symbol state and the sizes (lane 0)
-//           k_shb_scan           ONE workgroup: exclusive scan of the group's stream sizes onto the running payload size; the offset table; whether the
-//                                group still fits; behind the last group the header, the pad, the size word and the status (or the struck magic)
+//           k_blk_scan           ONE workgroup (hsrle_blockscan.hip.h): exclusive scan of the group's stream sizes onto the running payload size; the offset
+//                                table; whether the group still fits; behind the last group the header, the pad, the size word and the status (or the
+//                                struck magic)
 //           k_shb_write          per block: zero, emit, raw, place -- straight to the stream's final address
-//   decode  k_shb_begin          the status word: DONE
+//   decode  k_blk_begin          the status word: DONE
 //           k_shb_decode         per block: its table entry (trusted in nothing), walk -- every verdict, before anything is written --, the serial symbol
 //                                state (lane 0: a block has few records), the two expansions
-// Inside a kernel the passes of a block meet through global memory of the SAME workgroup: a device-scope fence and a barrier stand between them.
+// Inside a kernel the passes of a block meet through global memory of the SAME workgroup: blk_pass_edge stands between them.
 #pragma once
 
 #include "hsrle_rle8sh.hip.h"
+#include "hsrle_blockscan.hip.h"
 
 namespace hsrle {
 
-constexpr uint32_t kShbHeader = 64u, kShbPad = 32u;
-constexpr uint32_t kShbScanThreads = 1024u;
+constexpr uint32_t kShbHeader = kBlkHeader;
 // words of a slot's control block behind those of the passes ([0..4]): the size and status words the single-stream passes write, the stream's place
-constexpr uint32_t kShbSize = 8u, kShbStatus = 9u, kShbAtLo = 10u, kShbAtHi = 11u;
+constexpr uint32_t kShbSize = 8u, kShbStatus = 9u, kShbAtLo = kBlkAtLo, kShbAtHi = kBlkAtHi;
 
 struct ShbEncArgs
 {
@@ -49,18 +50,6 @@ struct ShbDecArgs
   uint64_t size, payloadSize, slotStride, offRec, offState;
   uint32_t blockSize, blockCount, first, count, maxRec, cap, win;   // blocks [first, first + count) of the container's blockCount
 };
-
-__device__ __forceinline__ void shb_pass_edge()
-{
-  __threadfence();
-  __syncthreads();
-}
-
-template <int UNUSED = 0>
-__global__ __launch_bounds__(64) void k_shb_begin(uint32_t *words, uint32_t count)
-{
-  if (threadIdx.x < count) words[threadIdx.x] = 0u;
-}
 
 __device__ __forceinline__ ShEncArgs shb_enc_args(const ShbEncArgs &g, uint32_t j)
 {
@@ -86,74 +75,18 @@ __global__ __launch_bounds__(64) void k_shb_decide_code(ShbEncArgs g)
 {
   const ShEncArgs a = shb_enc_args(g, blockIdx.x);
   d_she_decide(a);
-  shb_pass_edge();
+  blk_pass_edge();
   d_she_code(a);
 }
 
-template <int UNUSED = 0>
-__global__ __launch_bounds__(1024) void k_shb_scan(ShbEncArgs g)
+inline BlkScanArgs shb_scan_args(const ShbEncArgs &g)
 {
-  __shared__ uint64_t sSum[kShbScanThreads];
-  const uint32_t t = threadIdx.x, per = (g.count + kShbScanThreads - 1u) / kShbScanThreads;
-  const uint32_t lo = umin(t * per, g.count), hi = umin(lo + per, g.count);
-  const uint64_t base = (uint64_t)g.run[0] | (uint64_t)g.run[1] << 32;
-  int bad = g.run[2] != 0u;
-  uint64_t sum = 0u;
-  for (uint32_t j = lo; j < hi; j++)
-  {
-    const uint32_t *ctrl = (const uint32_t *)(g.slots + (uint64_t)j * g.slotStride);
-    if (ctrl[0] != 0u) bad = 1; else sum += ctrl[3];
-  }
-  bad = __syncthreads_or(bad);   // (every thread has read run[] in front of this barrier)
-  sSum[t] = sum;
-  __syncthreads();
-  for (uint32_t d = 1u; d < kShbScanThreads; d <<= 1)
-  {
-    const uint64_t v = t >= d ? sSum[t - d] : 0u;
-    __syncthreads();
-    sSum[t] += v;
-    __syncthreads();
-  }
-  const uint64_t total = sSum[kShbScanThreads - 1u], payload = (uint64_t)kShbHeader + 8ull * ((uint64_t)g.blockCount + 1u);
-  const bool fail = bad != 0 || payload + base + total + kShbPad > g.outCap;
-  uint64_t at = base + sSum[t] - sum;
-  for (uint32_t j = lo; j < hi; j++)
-  {
-    uint32_t *ctrl = (uint32_t *)(g.slots + (uint64_t)j * g.slotStride);
-    if (fail) { ctrl[0] = 1u; continue; }   // (gates the block's k_shb_write off)
-    st64(g.out + kShbHeader + 8ull * (g.first + j), at);   // (the host has seen that header, table and pad fit)
-    ctrl[kShbAtLo] = (uint32_t)at;
-    ctrl[kShbAtHi] = (uint32_t)(at >> 32);
-    at += ctrl[3];
-  }
-  if (t != 0u) return;
-  const uint64_t payloadSize = base + total;
-  g.run[0] = (uint32_t)payloadSize;
-  g.run[1] = (uint32_t)(payloadSize >> 32);
-  g.run[2] = fail ? 1u : 0u;
-  if (!g.last) return;
-  if (fail)
-  {
-    st64(g.out, 0u);   // struck: whatever the buffer held, it does not begin with the magic
-    *g.outSize = 0u;
-    *g.status = kShCapacity;
-    return;
-  }
-  const uint64_t totalSize = payload + payloadSize + kShbPad;
-  st64(g.out + kShbHeader + 8ull * g.blockCount, payloadSize);
-  st64(g.out, 0x424853454C525348ull);   // "HSRLESHB"
-  st32(g.out + 8, 1u);
-  st32(g.out + 12, 0u);
-  st64(g.out + 16, g.inSize);
-  st32(g.out + 24, g.blockSize);
-  st32(g.out + 28, g.blockCount);
-  st64(g.out + 32, payloadSize);
-  st64(g.out + 40, totalSize);
-  st64(g.out + 48, 0u);
-  st64(g.out + 56, 0u);
-  for (uint32_t k = 0; k < kShbPad; k += 8u) st64(g.out + payload + payloadSize + k, 0u);
-  *g.outSize = totalSize;
-  *g.status = kShDone;
+  BlkScanArgs b;
+  b.out = g.out; b.slots = g.slots; b.run = g.run; b.outSize = g.outSize; b.status = g.status;
+  b.inSize = g.inSize; b.outCap = g.outCap; b.slotStride = g.slotStride;
+  b.magic = 0x424853454C525348ull;   // "HSRLESHB"
+  b.blockSize = g.blockSize; b.blockCount = g.blockCount; b.first = g.first; b.count = g.count; b.last = g.last;
+  return b;
 }
 
 template <int UNUSED = 0>
@@ -165,10 +98,10 @@ __global__ __launch_bounds__(64) void k_shb_write(ShbEncArgs g)
   a.out = g.out + kShbHeader + 8ull * ((uint64_t)g.blockCount + 1u) + at;
   const uint32_t lane = threadIdx.x, bitWords = (a.ctrl[4] + 3u) / 4u, records = a.ctrl[2], chunks = (a.size + 15u) / 16u;
   for (uint32_t i = lane; i < bitWords; i += 64u) d_she_zero(a, i);
-  shb_pass_edge();   // (the token bits are ORed into the zeroed words)
+  blk_pass_edge();   // (the token bits are ORed into the zeroed words)
   for (uint32_t i = lane; i < records; i += 64u) d_she_emit(a, i);
   for (uint32_t i = lane; i < chunks; i += 64u) d_she_raw(a, i);
-  shb_pass_edge();
+  blk_pass_edge();
   for (uint32_t i = lane; i < bitWords; i += 64u) d_she_place(a, i);   // (the terminator's bits: at least one word, so lane 0 writes the header)
 }
 
@@ -177,18 +110,14 @@ __global__ __launch_bounds__(64) void k_shb_decode(ShbDecArgs g)
 {
   uint8_t *ws = g.slots + (uint64_t)blockIdx.x * g.slotStride;
   const uint32_t b = g.first + blockIdx.x, lane = threadIdx.x;
-  const uint8_t *table = g.container + kShbHeader;
-  const uint64_t o0 = sh_uniform64(ld64(table + 8ull * b)), o1 = sh_uniform64(ld64(table + 8ull * b + 8u));
-  const bool entry = o0 <= o1 && o1 <= g.payloadSize;   // a bad entry: a stream of no bytes, which the walk refuses without reading it
-  const uint64_t at = (uint64_t)b * g.blockSize, left = g.size - at, len = entry ? o1 - o0 : 0u;
+  const uint64_t at = (uint64_t)b * g.blockSize, left = g.size - at;
   ShDecArgs a;
-  a.stream = table + 8ull * ((uint64_t)g.blockCount + 1u) + (entry ? o0 : 0u);
+  a.stream = blk_stream(g.container, g.blockCount, g.payloadSize, b, a.streamCap);
   a.out = g.out + at;
   a.rec = (uint4 *)(ws + g.offRec);
   a.st = (uint2 *)(ws + g.offState);
   a.ctrl = (uint32_t *)ws;
   a.status = a.ctrl + kShbStatus;
-  a.streamCap = len > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)len;   // (S of the passes is capped by the ENTRY, never by the container)
   a.size = left < g.blockSize ? (uint32_t)left : g.blockSize;
   a.maxRec = g.maxRec; a.cap = g.cap; a.win = g.win; a.force = 1u;
   d_sh_walk(a);
@@ -197,10 +126,10 @@ __global__ __launch_bounds__(64) void k_shb_decode(ShbDecArgs g)
     a.ctrl[2] = 1u;   // the serial symbol pass is this decoder's only one
     if (a.ctrl[0] != kShDone) atomicOr(g.status, kShMalformed);
   }
-  shb_pass_edge();
+  blk_pass_edge();
   if (a.ctrl[0] != kShDone) return;   // a malformed block: none of its bytes is written
   d_sh_state(a);
-  shb_pass_edge();
+  blk_pass_edge();
   const uint32_t chunks = (a.size + 15u) / 16u, records = a.ctrl[1];
   for (uint32_t i = lane; i < chunks; i += 64u) d_sh_expand_blocks(a, i);
   for (uint32_t i = lane; i < records; i += 64u) d_sh_expand_sym<1>(a, i);

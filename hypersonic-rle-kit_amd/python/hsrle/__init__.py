@@ -44,7 +44,7 @@ class ContainerInfo(ctypes.Structure):
 
 
 class Rle8ShBlocksInfo(ctypes.Structure):
-    """hsrle_rle8_sh_blocks_info_t: the header of an rle8_sh block container."""
+    """hsrle_rle8_sh_blocks_info_t: the header of an rle8_sh block container, and of an rle8_mmtf128 block container (the fields are the same)."""
 
     _fields_ = [
         ("uncompressedSize", ctypes.c_uint64),
@@ -174,7 +174,7 @@ def _signatures():
         "hsrle_rle8m_compress_dev_async": (ci, [vp, u32, u32, vp, u64, vp, u64, vp, vp]),
         "hsrle_rle8m_info_dev": (ci, [vp, u64, r8m, vp]),
         "hsrle_rle8m_decompress_dev_async": (ci, [vp, r8m, vp, u64, vp, vp]),
-        # 5. the stream codecs: the mmtf transforms, rle8_mmtf128, rle8_sh and its block container
+        # 5. the stream codecs: the mmtf transforms, rle8_mmtf128, rle8_sh and the block containers of the two
         "hsrle_mmtf_workspace_size": (u64, [ci, u64]),
         "hsrle_mmtf_dev_async": (ci, [ci, ci, vp, u64, vp, vp, u64, vp]),
         "hsrle_mmtf_tuning": (None, [u32]),
@@ -197,6 +197,10 @@ def _signatures():
         "hsrle_rle8_sh_decompress_blocks_host": (ci, [vp, u64, vp, u64, P(u64)]),
         "hsrle_rle8_sh_blocks_tuning": (None, [u32]),
     }
+    # the rle8_mmtf128 block container: the rle8_sh block container's calling shapes (and its info struct) under its own names
+    for tail in ("blocks_bound", "blocks_workspace_size", "blocks_info_host", "blocks_info_dev", "compress_blocks_dev_async", "decompress_blocks_dev_async",
+                 "compress_blocks_host", "decompress_blocks_host", "blocks_tuning"):
+        table["hsrle_rle8_mmtf128_" + tail] = table["hsrle_rle8_sh_" + tail]
     for nm in ("mmtf_bounds", "bitmmtf_bounds", "rle8_mmtf128_compress_bounds", "rle8_mmtf256_compress_bounds", "rle8_sh_bounds"):
         table[nm] = (u32, [u32])
     # the rule of the reference-named host-pointer functions (src/rle.h): (pIn, inSize, pOut, outSize) -> size, 0 = failure
@@ -1036,4 +1040,76 @@ def rle8_sh_blocks_decompress_host(container, out_cap):
     out = ctypes.create_string_buffer(max(out_cap, 1))
     size = ctypes.c_uint64(0)
     rc = _lib().hsrle_rle8_sh_decompress_blocks_host(container, len(container), out, out_cap, ctypes.byref(size))
+    return rc, out.raw[: size.value] if rc == OK else b""
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the rle8_mmtf128 block container: many independent rle8_mmtf128 streams per call, identity lists at every block start (include/hsrle.h section 5)
+
+def rle8_mmtf128_blocks_bound(n, block_size=0):
+    """hsrle_rle8_mmtf128_blocks_bound: a container capacity that always suffices (0: bad block size, n == 0, too many blocks).  block_size 0 = 4096."""
+    return int(_lib().hsrle_rle8_mmtf128_blocks_bound(n, block_size))
+
+
+def rle8_mmtf128_blocks_workspace_size(decode, n, block_size=0):
+    """hsrle_rle8_mmtf128_blocks_workspace_size: bytes of device workspace; a function of min(blocks, blocks in flight) and the block size."""
+    return int(_lib().hsrle_rle8_mmtf128_blocks_workspace_size(1 if decode else 0, n, block_size))
+
+
+def rle8_mmtf128_blocks_tuning(blocks_in_flight=0):
+    """hsrle_rle8_mmtf128_blocks_tuning: blocks per group (0 = the default).  Any value gives the same bytes.  Process-global, for tests."""
+    _lib().hsrle_rle8_mmtf128_blocks_tuning(blocks_in_flight)
+
+
+def rle8_mmtf128_blocks_info(container):
+    """Rle8ShBlocksInfo (both block containers share it) of an rle8_mmtf128 block container in a CUDA tensor (reads the header, synchronises), a CPU tensor or bytes."""
+    info = Rle8ShBlocksInfo()
+    if hasattr(container, "is_cuda"):
+        if container.is_cuda:
+            rc = _lib().hsrle_rle8_mmtf128_blocks_info_dev(ctypes.c_void_p(container.data_ptr()), container.numel(), ctypes.byref(info), _stream_ptr())
+        else:
+            rc = _lib().hsrle_rle8_mmtf128_blocks_info_host(ctypes.c_void_p(container.data_ptr()), container.numel(), ctypes.byref(info))
+    else:
+        b = bytes(container)
+        rc = _lib().hsrle_rle8_mmtf128_blocks_info_host(b, len(b), ctypes.byref(info))
+    if rc != OK:
+        raise HsrleError(rc, "hsrle_rle8_mmtf128_blocks_info")
+    return info
+
+
+def rle8_mmtf128_blocks_compress_dev(src, dst, out_size, status, ws, block_size=0, stream=None):
+    """hsrle_rle8_mmtf128_compress_blocks_dev_async: enqueue the compression of the CUDA uint8 tensor `src` into the container buffer `dst`
+    (rle8_mmtf128_blocks_bound always suffices).  out_size: CUDA int64 tensor of one element, receives the container's size (0: it did not fit);
+    status: CUDA int32 tensor of one element, receives RLE8_MMTF_DONE / RLE8_MMTF_CAPACITY."""
+    for t, what in ((src, "src"), (dst, "dst"), (ws, "ws")):
+        _check_u8_cuda(t, what)
+    _call("hsrle_rle8_mmtf128_compress_blocks_dev_async", src, src.numel(), block_size, dst, dst.numel(), out_size, status, ws, ws.numel(), stream=stream)
+
+
+def rle8_mmtf128_blocks_decompress_dev(container, info, dst, status, ws, first_block=0, block_count=None, stream=None):
+    """hsrle_rle8_mmtf128_decompress_blocks_dev_async: enqueue the decompression of blocks [first_block, first_block + block_count) of the container in
+    the CUDA uint8 tensor `container` into `dst` (>= info.uncompressedSize bytes; block i lands at i * blockSize).  status: CUDA int32 tensor of one
+    element, receives RLE8_MMTF_DONE / RLE8_MMTF_MALFORMED."""
+    for t, what in ((container, "container"), (dst, "dst"), (ws, "ws")):
+        _check_u8_cuda(t, what)
+    count = info.blockCount - first_block if block_count is None else block_count
+    _call("hsrle_rle8_mmtf128_decompress_blocks_dev_async", container, ctypes.byref(info), first_block, count, dst, dst.numel(), status, ws, ws.numel(), stream=stream)
+
+
+def rle8_mmtf128_blocks_compress_host(data, block_size=0, out_cap=None):
+    """hsrle_rle8_mmtf128_compress_blocks_host: (status, container bytes) of host bytes.  out_cap defaults to rle8_mmtf128_blocks_bound."""
+    data = bytes(data)
+    cap = rle8_mmtf128_blocks_bound(len(data), block_size) if out_cap is None else out_cap
+    out = ctypes.create_string_buffer(max(cap, 1))
+    total = ctypes.c_uint64(0)
+    rc = _lib().hsrle_rle8_mmtf128_compress_blocks_host(data, len(data), block_size, out, cap, ctypes.byref(total))
+    return rc, out.raw[: total.value] if rc == OK else b""
+
+
+def rle8_mmtf128_blocks_decompress_host(container, out_cap):
+    """hsrle_rle8_mmtf128_decompress_blocks_host: (status, uncompressed bytes) of a container in host bytes."""
+    container = bytes(container)
+    out = ctypes.create_string_buffer(max(out_cap, 1))
+    size = ctypes.c_uint64(0)
+    rc = _lib().hsrle_rle8_mmtf128_decompress_blocks_host(container, len(container), out, out_cap, ctypes.byref(size))
     return rc, out.raw[: size.value] if rc == OK else b""

@@ -820,6 +820,7 @@ void hsrle_rle8_sh_tuning(uint32_t stretchSymbols, uint32_t walkWindow, uint32_t
  * The _host calls stage host buffers per device like the functions above: HSRLE_OK / HSRLE_ERR_*; a malformed block is HSRLE_ERR_FORMAT.
  * hsrle_rle8_sh_blocks_tuning: blocks in flight (0 = the default: 32 MiB of input per group, at least 256 and at most 8192 blocks -- DESIGN.md 4.9).
  *   Any value gives the same bytes.  PROCESS-GLOBAL, for tests.
+ * BOTH block containers of this section (this one and the rle8_mmtf128 block container below) share hsrle_rle8_sh_blocks_info_t: the fields are the same.
  */
 typedef struct hsrle_rle8_sh_blocks_info
 {
@@ -838,6 +839,51 @@ int hsrle_rle8_sh_decompress_blocks_dev_async(const void *dContainer, const hsrl
 int hsrle_rle8_sh_compress_blocks_host(const void *pIn, uint64_t inSize, uint32_t blockSize, void *pOut, uint64_t outCapacity, uint64_t *pContainerSize);
 int hsrle_rle8_sh_decompress_blocks_host(const void *pContainer, uint64_t containerSize, void *pOut, uint64_t outCapacity, uint64_t *pUncompressedSize);
 void hsrle_rle8_sh_blocks_tuning(uint32_t blocksInFlight);
+
+/*
+ * The rle8_mmtf128 BLOCK CONTAINER: many independent rle8_mmtf128 streams per call -- the throughput path of that codec.  The layout is the rle8_sh block
+ * container's, field for field, under the magic "HSRLEMFB", version 1: 64 header bytes, uint64_t offset[blockCount + 1] relative to the payload, the
+ * block streams back to back at any byte address, 32 zero bytes; the info struct is hsrle_rle8_sh_blocks_info_t itself.  Block stream i is EXACTLY what
+ * this library's rle8_mmtf128_compress returns for input bytes [i B, min((i + 1) B, n)), its own 8-byte header included: the first packet's start
+ * value is zero and the move-to-front lists are the IDENTITY at the start of every block.  Only the last block can have size % 16 tail ranks; it may be
+ * shorter than 16 bytes, and then has no rows: a first COPY 0x06, the terminator, the tail.  With the lists restarted the transform of a block needs no
+ * state table and no scan, the span scan of a block is one wave's work and every block's header chain is walked by a wave of its own: none of the
+ * single stream's serial passes is left.  The restart costs ratio: every block pays again for bringing its symbols to the front of its lists.
+ * Each family's info functions refuse the other two magics ("HSRLEKIT", "HSRLESHB", "HSRLEMFB").  blockSize: a multiple of 128, 128 .. 2^20; 0 means 4096.
+ * bound: header + table + the sum of (bytes of block i + 13) + 32: always suffices (inSize + 13 suffices for one stream, see above).  0 for a bad block
+ *   size, inSize == 0 or a block count that does not fit 32 bits.
+ * workspace_size: a function of min(blocks, blocks in flight) and blockSize, NOT of inSize: a slot per block in flight -- its rank buffer (blockSize + 16),
+ *   and 32 bytes per span of 64 rows (compress) or 16 bytes per row for the packet records (decompress).  A decode of a block range needs the size
+ *   for (blocks of the range) * blockSize bytes.  0 where bound is 0.
+ * info_host / info_dev, the refusals of the two ENQUEUE-ONLY _dev_async calls and their order, the _host calls and their return values: as for the
+ *   rle8_sh block container above, word for word (a null pointer, a bad block size, inSize == 0, overlapping buffers, misaligned words, an info whose
+ *   fields contradict each other, a block range outside the container or of no blocks: HSRLE_ERR_ARGUMENT; a workspace too small, an outCapacity
+ *   under header + table + pad (compress) or under uncompressedSize (decompress): HSRLE_ERR_CAPACITY).  Nothing allocates, synchronises or reads
+ *   device memory; a HIP graph can capture the calls as a linear chain; every word a kernel reads was written by a kernel of the same call; workspace
+ *   contents do not matter; buffers at any byte address.  The status words are HSRLE_RLE8_MMTF_DONE / _MALFORMED / _CAPACITY.
+ * compress: *dOutSize receives totalSize and *dStatus HSRLE_RLE8_MMTF_DONE; the container is complete and written straight to its final address,
+ *   nothing at or beyond totalSize.  If it does not fit outCapacity: HSRLE_RLE8_MMTF_CAPACITY, *dOutSize 0, the first 8 bytes of dOut are not the
+ *   magic, nothing is written at or beyond outCapacity and what lies inside it is unspecified.
+ * decompress: decodes blocks [firstBlock, firstBlock + blockCount) into dOut + firstBlock * blockSize.  The offset table is trusted in nothing.  A block
+ *   is MALFORMED when its entry is bad (offset[i] > offset[i + 1] or offset[i + 1] > payloadSize) or its stream breaks any refusal rule of
+ *   hsrle_rle8_mmtf128_decompress_dev_async, applied with the block's own size and its entry's length; NONE of its output bytes is written (the walk's
+ *   verdict gates the block's expansion and its inverse transform), the other blocks are decoded, and *dStatus receives HSRLE_RLE8_MMTF_MALFORMED
+ *   if any block was.  Never a byte outside the decoded range of dOut is written.
+ * hsrle_rle8_mmtf128_blocks_tuning: blocks in flight (0 = the default of the rle8_sh block container).  hsrle_rle8_mmtf_tuning (rows per span) is
+ *   honoured by the per-block compress passes and changes the compress workspace; hsrle_mmtf_tuning has nothing to choose here: the segment is the
+ *   block.  Any value gives the same bytes.  PROCESS-GLOBAL, for tests.
+ */
+uint64_t hsrle_rle8_mmtf128_blocks_bound(uint64_t inSize, uint32_t blockSize);
+uint64_t hsrle_rle8_mmtf128_blocks_workspace_size(int decode, uint64_t inSize, uint32_t blockSize);
+int hsrle_rle8_mmtf128_blocks_info_host(const void *pContainer, uint64_t containerSize, hsrle_rle8_sh_blocks_info_t *pInfo);
+int hsrle_rle8_mmtf128_blocks_info_dev(const void *dContainer, uint64_t containerSize, hsrle_rle8_sh_blocks_info_t *pInfo, void *stream);
+int hsrle_rle8_mmtf128_compress_blocks_dev_async(const void *dIn, uint64_t inSize, uint32_t blockSize, void *dOut, uint64_t outCapacity, uint64_t *dOutSize, uint32_t *dStatus,
+                                                 void *dWorkspace, uint64_t workspaceSize, void *stream);
+int hsrle_rle8_mmtf128_decompress_blocks_dev_async(const void *dContainer, const hsrle_rle8_sh_blocks_info_t *info, uint32_t firstBlock, uint32_t blockCount, void *dOut,
+                                                   uint64_t outCapacity, uint32_t *dStatus, void *dWorkspace, uint64_t workspaceSize, void *stream);
+int hsrle_rle8_mmtf128_compress_blocks_host(const void *pIn, uint64_t inSize, uint32_t blockSize, void *pOut, uint64_t outCapacity, uint64_t *pContainerSize);
+int hsrle_rle8_mmtf128_decompress_blocks_host(const void *pContainer, uint64_t containerSize, void *pOut, uint64_t outCapacity, uint64_t *pUncompressedSize);
+void hsrle_rle8_mmtf128_blocks_tuning(uint32_t blocksInFlight);
 
 int hsrle_kernel_waves_per_cu(int codec, int decode);
 const char *hsrle_version(void);
