@@ -181,11 +181,13 @@ struct Staging
 // The staged trip of a host-pointer call whose verdict is in its status words: reserve, copy up, enqueue(s) -> HSRLE_* code, read `wordCount` status words
 // (0: the call has none), judge(words, n) -> HSRLE_* code and the bytes to hand back, copy them down.  Returns how far it got as a code: HSRLE_ERR_DEVICE for
 // a reservation or copy that failed, else the first code of enqueue / judge that is not HSRLE_OK, else HSRLE_OK with *copied bytes in pOut.
+// inExtra: input staging behind the inBytes, for a second input that enqueue copies up itself (Staging::up with an offset).
 template <typename Enqueue, typename Judge>
-static int staged_call(const void *pIn, uint64_t inBytes, uint64_t outBytes, uint64_t wsBytes, void *pOut, uint32_t wordCount, Enqueue enqueue, Judge judge, uint64_t *copied)
+static int staged_call(const void *pIn, uint64_t inBytes, uint64_t outBytes, uint64_t wsBytes, void *pOut, uint32_t wordCount, Enqueue enqueue, Judge judge, uint64_t *copied,
+                       uint64_t inExtra = 0)
 {
   Staging s;
-  if (!s.reserve(inBytes, outBytes) || !s.reserve_ws(wsBytes) || !s.up(pIn, inBytes))
+  if (!s.reserve(inBytes + inExtra, outBytes) || !s.reserve_ws(wsBytes) || !s.up(pIn, inBytes))
     return HSRLE_ERR_DEVICE;
   int rc = enqueue(s);
   if (rc != HSRLE_OK)
@@ -206,19 +208,43 @@ static int staged_call(const void *pIn, uint64_t inBytes, uint64_t outBytes, uin
 // the single-stream codecs (rle8_sh: hsrle_capi_sh.h, rle8_mmtf128: hsrle_capi_mmtf.h): one device entry, one host-pointer body, per direction
 
 // The check order of both directions: a null pointer or no plan -> ARGUMENT; overlap or a misaligned word -> ARGUMENT; output or workspace too small -> CAPACITY.
+// (the checks alone, with the plan they made: the indexed calls of rle8_mmtf128 put their own between them and the enqueue)
 template <typename Plan, typename PlanFn>
-static int stream_compress_entry(PlanFn plan, hipError_t (*enqueue)(const Plan &, const uint8_t *, uint8_t *, uint32_t, uint32_t *, uint32_t *, uint8_t *, hipStream_t), const void *dIn,
-                                 uint64_t inSize, void *dOut, uint64_t outCapacity, uint32_t *dOutSize, uint32_t *dStatus, void *dWorkspace, uint64_t workspaceSize, void *stream)
+static int stream_compress_check(PlanFn plan, const void *dIn, uint64_t inSize, void *dOut, uint64_t outCapacity, uint32_t *dOutSize, uint32_t *dStatus, void *dWorkspace,
+                                 uint64_t workspaceSize, Plan &p)
 {
-  Plan p;
   if (dIn == nullptr || dOut == nullptr || dOutSize == nullptr || dStatus == nullptr || dWorkspace == nullptr || !plan(inSize, p))
     return HSRLE_ERR_ARGUMENT;
   if (ranges_overlap(dIn, inSize, dOut, outCapacity) || !word_aligned(dOutSize, 4) || !word_aligned(dStatus, 4))
     return HSRLE_ERR_ARGUMENT;
   if (outCapacity < inSize + 8u || workspaceSize < p.total)
     return HSRLE_ERR_CAPACITY;
+  return HSRLE_OK;
+}
+
+template <typename Plan, typename PlanFn>
+static int stream_compress_entry(PlanFn plan, hipError_t (*enqueue)(const Plan &, const uint8_t *, uint8_t *, uint32_t, uint32_t *, uint32_t *, uint8_t *, hipStream_t), const void *dIn,
+                                 uint64_t inSize, void *dOut, uint64_t outCapacity, uint32_t *dOutSize, uint32_t *dStatus, void *dWorkspace, uint64_t workspaceSize, void *stream)
+{
+  Plan p;
+  const int rc = stream_compress_check(plan, dIn, inSize, dOut, outCapacity, dOutSize, dStatus, dWorkspace, workspaceSize, p);
+  if (rc != HSRLE_OK)
+    return rc;
   return enqueue(p, (const uint8_t *)dIn, (uint8_t *)dOut, clamp32(outCapacity), dOutSize, dStatus, workspace_start(dWorkspace), (hipStream_t)stream) == hipSuccess ? HSRLE_OK
                                                                                                                                                                   : HSRLE_ERR_DEVICE;
+}
+
+template <typename Plan, typename PlanFn>
+static int stream_decompress_check(PlanFn plan, const void *dStream, uint64_t streamSize, void *dOut, uint64_t outSize, uint32_t *dStatus, void *dWorkspace, uint64_t workspaceSize,
+                                   Plan &p)
+{
+  if (dStream == nullptr || dOut == nullptr || dStatus == nullptr || dWorkspace == nullptr || streamSize == 0u || !plan(outSize, p))
+    return HSRLE_ERR_ARGUMENT;
+  if (ranges_overlap(dStream, streamSize, dOut, outSize) || !word_aligned(dStatus, 4))
+    return HSRLE_ERR_ARGUMENT;
+  if (workspaceSize < p.total)
+    return HSRLE_ERR_CAPACITY;
+  return HSRLE_OK;
 }
 
 template <typename Plan, typename PlanFn>
@@ -226,12 +252,9 @@ static int stream_decompress_entry(PlanFn plan, hipError_t (*enqueue)(const Plan
                                    uint64_t streamSize, void *dOut, uint64_t outSize, uint32_t *dStatus, void *dWorkspace, uint64_t workspaceSize, void *stream)
 {
   Plan p;
-  if (dStream == nullptr || dOut == nullptr || dStatus == nullptr || dWorkspace == nullptr || streamSize == 0u || !plan(outSize, p))
-    return HSRLE_ERR_ARGUMENT;
-  if (ranges_overlap(dStream, streamSize, dOut, outSize) || !word_aligned(dStatus, 4))
-    return HSRLE_ERR_ARGUMENT;
-  if (workspaceSize < p.total)
-    return HSRLE_ERR_CAPACITY;
+  const int rc = stream_decompress_check(plan, dStream, streamSize, dOut, outSize, dStatus, dWorkspace, workspaceSize, p);
+  if (rc != HSRLE_OK)
+    return rc;
   return enqueue(p, (const uint8_t *)dStream, clamp32(streamSize), (uint8_t *)dOut, dStatus, workspace_start(dWorkspace), (hipStream_t)stream) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
 }
 

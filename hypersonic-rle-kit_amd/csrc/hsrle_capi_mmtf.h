@@ -131,6 +131,35 @@ static uint32_t rle8mmtf_bounds(uint32_t inSize) { return inSize > kRle8MmtfMaxI
 static bool rle8mmtf_enc_plan(uint64_t size, Rle8MmtfPlan &p) { return rle8mmtf_plan(0, size, p); }
 static bool rle8mmtf_dec_plan(uint64_t size, Rle8MmtfPlan &p) { return rle8mmtf_plan(1, size, p); }
 
+// ---- the entry index of an rle8_mmtf128 stream (kernels and layout: hsrle_rle8mmtf_index.hip.h) ----
+constexpr uint32_t kRmIndexDefaultSpacing = 1024u;   // rows: the fastest of 256 / 1024 / 4096 on the video-shaped 1 GiB decode (profiles/r18_rle8_mmtf_index.md)
+constexpr uint32_t kRmIndexCodec = HSRLE_RLE8_MMTF_INDEX_CODEC;   // hsrle_mono_index_info_t::codec of such an index: no id of the codec table
+
+// spacingRows as the calls take it -> rows per window, 0 = not a spacing
+static uint32_t rm_index_spacing(uint32_t spacingRows)
+{
+  if (spacingRows == 0u) return kRmIndexDefaultSpacing;
+  return (spacingRows % 64u != 0u || spacingRows > (1u << 20)) ? 0u : spacingRows;
+}
+// windows 1 .. of `spacing` rows that hold a row: the most entries
+static uint32_t rm_index_max_entries(uint64_t uncompressedSize, uint32_t spacing)
+{
+  const uint64_t rows = uncompressedSize / 16u;
+  return rows == 0u ? 0u : (uint32_t)((rows - 1u) / spacing);
+}
+static uint64_t rm_index_bound(uint64_t uncompressedSize, uint32_t spacingRows)
+{
+  const uint32_t spacing = rm_index_spacing(spacingRows);
+  return (spacing == 0u || uncompressedSize > kRle8MmtfMaxIn) ? 0u : 64u + 16ull * rm_index_max_entries(uncompressedSize, spacing);
+}
+// what a caller's header has to say before anything is planned from it (a size that does not go with the count: left to the device's comparison, INDEX)
+static bool rm_index_info_ok(const hsrle_mono_index_info_t &i)
+{
+  return i.version == 1u && i.codec == kRmIndexCodec && i.recordBytes == 16u && i.spacing != 0u && rm_index_spacing(i.spacing) == i.spacing && i.uncompressedSize != 0u &&
+         i.uncompressedSize <= kRle8MmtfMaxIn && i.recordCount <= rm_index_max_entries(i.uncompressedSize, i.spacing);
+}
+static bool rm_index_args_ok(const void *dIndex, uint64_t *dIndexSize) { return dIndex != nullptr && dIndexSize != nullptr && word_aligned(dIndexSize, 8); }
+
 static const StreamCodec kRle8MmtfCodec = { hsrle_rle8_mmtf128_workspace_size, hsrle_rle8_mmtf128_compress_dev_async, hsrle_rle8_mmtf128_decompress_dev_async, kRle8MmtfMaxIn, 8u,
                                             HSRLE_RLE8_MMTF_DONE };
 
@@ -156,6 +185,124 @@ int hsrle_rle8_mmtf128_decompress_dev_async(const void *dStream, uint64_t stream
                                             void *stream)
 {
   return stream_decompress_entry<Rle8MmtfPlan>(rle8mmtf_dec_plan, rle8mmtf_decompress_enqueue, dStream, streamSize, dOut, outSize, dStatus, dWorkspace, workspaceSize, stream);
+}
+
+uint64_t hsrle_rle8_mmtf128_index_bound(uint64_t uncompressedSize, uint32_t spacingRows) { return rm_index_bound(uncompressedSize, spacingRows); }
+
+int hsrle_rle8_mmtf128_index_info_host(const void *pIndex, uint64_t size, hsrle_mono_index_info_t *pInfo)
+{
+  if (pIndex == nullptr || pInfo == nullptr)
+    return HSRLE_ERR_ARGUMENT;
+  uint32_t w[16];
+  if (size < sizeof(w))
+    return HSRLE_ERR_FORMAT;
+  memcpy(w, pIndex, sizeof(w));
+  hsrle_mono_index_info_t i = {};
+  i.version = w[2]; i.codec = kRmIndexCodec;
+  i.uncompressedSize = w[4]; i.compressedSize = w[5];
+  i.spacing = w[6]; i.recordCount = w[7]; i.recordBytes = 16u;
+  i.indexBytes = (uint64_t)w[8] | (uint64_t)w[9] << 32;
+  bool zeros = true;
+  for (int k = 10; k < 16; k++) zeros = zeros && w[k] == 0u;
+  if (memcmp(w, "HSRLEMFI", 8) != 0 || w[3] != 64u || !zeros || !rm_index_info_ok(i) || i.indexBytes != 64u + 16ull * i.recordCount || i.compressedSize < 10u || i.indexBytes > size)
+    return HSRLE_ERR_FORMAT;
+  *pInfo = i;
+  return HSRLE_OK;
+}
+
+int hsrle_rle8_mmtf128_compress_indexed_dev_async(const void *dIn, uint64_t inSize, void *dOut, uint64_t outCapacity, uint32_t *dOutSize, uint32_t *dStatus, void *dWorkspace,
+                                                  uint64_t workspaceSize, uint32_t spacingRows, void *dIndex, uint64_t indexCapacity, uint64_t *dIndexSize, void *stream)
+{
+  Rle8MmtfPlan p;
+  const int rc = stream_compress_check(rle8mmtf_enc_plan, dIn, inSize, dOut, outCapacity, dOutSize, dStatus, dWorkspace, workspaceSize, p);
+  const uint32_t spacing = rm_index_spacing(spacingRows);
+  if (rc == HSRLE_ERR_ARGUMENT || spacing == 0u || !rm_index_args_ok(dIndex, dIndexSize) || ranges_overlap(dIndex, indexCapacity, dIn, inSize) ||
+      ranges_overlap(dIndex, indexCapacity, dOut, outCapacity))
+    return HSRLE_ERR_ARGUMENT;
+  if (rc != HSRLE_OK || indexCapacity < rm_index_bound(inSize, spacing))
+    return HSRLE_ERR_CAPACITY;
+  uint8_t *ws = workspace_start(dWorkspace);
+  hipStream_t st = (hipStream_t)stream;
+  if (rle8mmtf_compress_enqueue(p, (const uint8_t *)dIn, (uint8_t *)dOut, clamp32(outCapacity), dOutSize, dStatus, ws, st) != hipSuccess)
+    return HSRLE_ERR_DEVICE;
+  return rle8mmtf_index_emit_enqueue(p, (uint8_t *)dOut, dOutSize, ws, spacing, (uint8_t *)dIndex, dIndexSize, st) == hipSuccess ? HSRLE_OK : HSRLE_ERR_DEVICE;
+}
+
+int hsrle_rle8_mmtf128_index_build_dev_async(const void *dStream, uint64_t streamSize, uint64_t uncompressedSize, uint32_t spacingRows, void *dIndex, uint64_t indexCapacity,
+                                             uint64_t *dIndexSize, uint32_t *dStatus, void *stream)
+{
+  const uint32_t spacing = rm_index_spacing(spacingRows);
+  if (dStream == nullptr || dStatus == nullptr || streamSize == 0u || uncompressedSize == 0u || uncompressedSize > kRle8MmtfMaxIn || spacing == 0u ||
+      !rm_index_args_ok(dIndex, dIndexSize) || !word_aligned(dStatus, 4) || ranges_overlap(dIndex, indexCapacity, dStream, streamSize))
+    return HSRLE_ERR_ARGUMENT;
+  if (indexCapacity < rm_index_bound(uncompressedSize, spacing))
+    return HSRLE_ERR_CAPACITY;
+  return rle8mmtf_index_build_enqueue((const uint8_t *)dStream, clamp32(streamSize), (uint32_t)uncompressedSize, spacing, (uint8_t *)dIndex, dIndexSize, dStatus,
+                                      (hipStream_t)stream) == hipSuccess
+           ? HSRLE_OK
+           : HSRLE_ERR_DEVICE;
+}
+
+int hsrle_rle8_mmtf128_decompress_indexed_dev_async(const void *dStream, uint64_t streamSize, const void *dIndex, const hsrle_mono_index_info_t *info, void *dOut, uint64_t outSize,
+                                                    uint32_t *dStatus, void *dWorkspace, uint64_t workspaceSize, void *stream)
+{
+  Rle8MmtfPlan p;
+  const int rc = stream_decompress_check(rle8mmtf_dec_plan, dStream, streamSize, dOut, outSize, dStatus, dWorkspace, workspaceSize, p);
+  if (rc == HSRLE_ERR_ARGUMENT || dIndex == nullptr || info == nullptr || !rm_index_info_ok(*info) || info->uncompressedSize != outSize ||
+      ranges_overlap(dIndex, info->indexBytes, dOut, outSize))
+    return HSRLE_ERR_ARGUMENT;
+  if (rc != HSRLE_OK)
+    return rc;
+  return rle8mmtf_decompress_indexed_enqueue(p, (const uint8_t *)dStream, clamp32(streamSize), (const uint8_t *)dIndex, info->compressedSize, info->spacing, info->recordCount,
+                                             (uint8_t *)dOut, dStatus, workspace_start(dWorkspace), (hipStream_t)stream) == hipSuccess
+           ? HSRLE_OK
+           : HSRLE_ERR_DEVICE;
+}
+
+// The two host-pointer calls: the staged trip.  Status word and index size word: Staging::status[0] and [2 .. 3].
+int hsrle_rle8_mmtf128_index_build_host(const void *pStream, uint64_t streamSize, uint32_t spacingRows, void *pIndex, uint64_t indexCapacity, uint64_t *pIndexSize)
+{
+  if (pStream == nullptr || pIndex == nullptr || pIndexSize == nullptr || streamSize < 8u || streamSize > 0xFFFFFFFFull)
+    return HSRLE_ERR_ARGUMENT;
+  uint32_t hdr[2];
+  memcpy(hdr, pStream, 8);
+  const uint64_t bound = rm_index_bound(hdr[0], spacingRows);
+  if (hdr[0] == 0u || bound == 0u)
+    return rm_index_spacing(spacingRows) == 0u ? HSRLE_ERR_ARGUMENT : HSRLE_ERR_FORMAT;
+  if (indexCapacity < bound)
+    return HSRLE_ERR_CAPACITY;
+  if (!device_ok())
+    return HSRLE_ERR_DEVICE;
+  return staged_call(
+    pStream, streamSize, bound, 256u, pIndex, 4u,
+    [&](Staging &s) { return hsrle_rle8_mmtf128_index_build_dev_async(s.in, streamSize, hdr[0], spacingRows, s.out, bound, (uint64_t *)(s.status + 2), s.status, nullptr); },
+    [&](const uint32_t *h, uint64_t &n) { n = (uint64_t)h[2] | (uint64_t)h[3] << 32; return h[0] != HSRLE_RLE8_MMTF_DONE || n < 64u || n > bound ? HSRLE_ERR_FORMAT : HSRLE_OK; },
+    pIndexSize);
+}
+
+int hsrle_rle8_mmtf128_decompress_indexed_host(const void *pStream, uint64_t streamSize, const void *pIndex, uint64_t indexSize, void *pOut, uint64_t outCapacity,
+                                               uint64_t *pUncompressedSize)
+{
+  if (pStream == nullptr || pIndex == nullptr || pOut == nullptr || pUncompressedSize == nullptr || streamSize < 8u || streamSize > 0xFFFFFFFFull)
+    return HSRLE_ERR_ARGUMENT;
+  hsrle_mono_index_info_t info;
+  const int rc = hsrle_rle8_mmtf128_index_info_host(pIndex, indexSize, &info);
+  if (rc != HSRLE_OK)
+    return rc;
+  if (outCapacity < info.uncompressedSize)
+    return HSRLE_ERR_CAPACITY;
+  const uint64_t need = hsrle_rle8_mmtf128_workspace_size(1, info.uncompressedSize), indexAt = align_up(streamSize, 256);
+  if (need == 0u || !device_ok())
+    return HSRLE_ERR_DEVICE;
+  return staged_call(
+    pStream, streamSize, info.uncompressedSize, need, pOut, 1u,
+    [&](Staging &s) {
+      if (!s.up(pIndex, info.indexBytes, indexAt))
+        return (int)HSRLE_ERR_DEVICE;
+      return hsrle_rle8_mmtf128_decompress_indexed_dev_async(s.in, streamSize, s.in + indexAt, &info, s.out, info.uncompressedSize, s.status, s.ws, s.wsSize, nullptr);
+    },
+    [&](const uint32_t *h, uint64_t &n) { n = info.uncompressedSize; return h[0] != HSRLE_RLE8_MMTF_DONE ? HSRLE_ERR_FORMAT : HSRLE_OK; }, pUncompressedSize,
+    indexAt - streamSize + info.indexBytes);
 }
 
 uint32_t rle8_mmtf128_compress_bounds(const uint32_t inSize) { return rle8mmtf_bounds(inSize); }

@@ -31,6 +31,15 @@ struct Rle8MmtfPlan
 hipError_t rle8mmtf_compress_enqueue(const Rle8MmtfPlan &p, const uint8_t *dIn, uint8_t *dOut, uint32_t outCap, uint32_t *dOutSize, uint32_t *dStatus, uint8_t *ws, hipStream_t st);
 hipError_t rle8mmtf_decompress_enqueue(const Rle8MmtfPlan &p, const uint8_t *dStream, uint32_t streamCap, uint8_t *dOut, uint32_t *dStatus, uint8_t *ws, hipStream_t st);
 
+// The entry index of one rle8_mmtf128 stream (kernels: hsrle_rle8mmtf_index.hip.h; launched by inst_rle8mmtfi.hip).  index_emit: behind compress_enqueue of the
+// same plan, workspace and stream.  index_build: one wave, no workspace.  decompress_indexed: the decode plan and workspace of decompress_enqueue; streamSize,
+// spacing, entries: the index header the caller holds.
+hipError_t rle8mmtf_index_emit_enqueue(const Rle8MmtfPlan &p, uint8_t *dOut, uint32_t *dOutSize, uint8_t *ws, uint32_t spacing, uint8_t *dIndex, uint64_t *dIndexSize, hipStream_t st);
+hipError_t rle8mmtf_index_build_enqueue(const uint8_t *dStream, uint32_t streamCap, uint32_t size, uint32_t spacing, uint8_t *dIndex, uint64_t *dIndexSize, uint32_t *dStatus,
+                                        hipStream_t st);
+hipError_t rle8mmtf_decompress_indexed_enqueue(const Rle8MmtfPlan &p, const uint8_t *dStream, uint32_t streamCap, const uint8_t *dIndex, uint32_t streamSize, uint32_t spacing,
+                                               uint32_t entries, uint8_t *dOut, uint32_t *dStatus, uint8_t *ws, hipStream_t st);
+
 // The blocked form (hsrle_capi_mmtfb.h plans, inst_rle8mmtfb.hip launches, kernels: hsrle_rle8mmtfb.hip.h).  Workspace, from its 256-byte aligned start:
 // 256 bytes of words for the whole call, then `inFlight` SLOTS: control words, the block's rank buffer, then -- encode: the span summaries and the span
 // results of a block; decode: its packet records.

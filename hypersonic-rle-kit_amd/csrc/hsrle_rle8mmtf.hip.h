@@ -130,6 +130,7 @@ __device__ __forceinline__ uint32_t rm_wave_sum(uint32_t x)
 //                               y = OR in front of the first start | OR from the last start on << 8,  z = bytes of the closed packets
 // per span, from k_rm_scan:     x = stream offset of the first packet that starts in the span, y = count of its open packet, z = its width code,
 //                               w = the last span before this one in which a packet starts
+// (behind k_rm_emit the entry index's k_rm_index_count reuses y and z: hsrle_rle8mmtf_index.hip.h)
 struct RmEncArgs
 {
   const uint8_t *ranks;   // 16-byte aligned, rows * 16 + tail bytes

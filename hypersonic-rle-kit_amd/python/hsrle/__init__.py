@@ -182,6 +182,13 @@ def _signatures():
         "hsrle_rle8_mmtf128_compress_dev_async": stream_enc,
         "hsrle_rle8_mmtf128_decompress_dev_async": stream_dec,
         "hsrle_rle8_mmtf_tuning": (None, [u32]),
+        "hsrle_rle8_mmtf128_index_bound": (u64, [u64, u32]),
+        "hsrle_rle8_mmtf128_index_info_host": (ci, [vp, u64, idx]),
+        "hsrle_rle8_mmtf128_compress_indexed_dev_async": (ci, stream_enc[1][:-1] + [u32, vp, u64, vp, vp]),
+        "hsrle_rle8_mmtf128_index_build_dev_async": (ci, [vp, u64, u64, u32, vp, u64, vp, vp, vp]),
+        "hsrle_rle8_mmtf128_decompress_indexed_dev_async": (ci, [vp, u64, vp, idx, vp, u64, vp, vp, u64, vp]),
+        "hsrle_rle8_mmtf128_index_build_host": (ci, [vp, u64, u32, vp, u64, P(u64)]),
+        "hsrle_rle8_mmtf128_decompress_indexed_host": (ci, [vp, u64, vp, u64, vp, u64, P(u64)]),
         "hsrle_rle8_sh_workspace_size": (u64, [ci, u64]),
         "hsrle_rle8_sh_capacity": (u64, [u64]),
         "hsrle_rle8_sh_compress_dev_async": stream_enc,
@@ -906,6 +913,72 @@ def rle8_mmtf128_decompress_dev(src, dst, status, ws, stream=None):
     for t, what in ((src, "src"), (dst, "dst"), (ws, "ws")):
         _check_u8_cuda(t, what)
     _call("hsrle_rle8_mmtf128_decompress_dev_async", src, src.numel(), dst, dst.numel(), status, ws, ws.numel(), stream=stream)
+
+
+# the entry index of one rle8_mmtf128 stream: a sidecar that lets a wave per stretch follow the header chain (include/hsrle.h section 5)
+
+RLE8_MMTF_INDEX = 3
+RLE8_MMTF_INDEX_CODEC = 0xFFFFFFFF
+Rle8MmtfIndexInfo = MonoIndexInfo                                        # hsrle_rle8_mmtf128_index_info_t is hsrle_mono_index_info_t
+
+
+def rle8_mmtf128_index_bound(size, spacing_rows=0):
+    """hsrle_rle8_mmtf128_index_bound: an index capacity that always suffices (0: bad spacing, size above 2^30).  spacing_rows 0 = the default."""
+    return int(_lib().hsrle_rle8_mmtf128_index_bound(size, spacing_rows))
+
+
+def rle8_mmtf128_index_info(index):
+    """hsrle_rle8_mmtf128_index_info_host on index bytes: the validated header as Rle8MmtfIndexInfo; raises HsrleError(ERR_FORMAT) for a bad one."""
+    index = bytes(index)
+    info = Rle8MmtfIndexInfo()
+    rc = _lib().hsrle_rle8_mmtf128_index_info_host(index, len(index), ctypes.byref(info))
+    if rc != OK:
+        raise HsrleError(rc, "hsrle_rle8_mmtf128_index_info_host")
+    return info
+
+
+def rle8_mmtf128_compress_indexed_dev(src, dst, out_size, status, ws, index, index_size, spacing_rows=0, stream=None):
+    """hsrle_rle8_mmtf128_compress_indexed_dev_async: rle8_mmtf128_compress_dev and the stream's entry index into the CUDA uint8 tensor `index`
+    (>= rle8_mmtf128_index_bound bytes).  index_size: CUDA int64 tensor of one element, receives the index size (0: the stream did not fit)."""
+    for t, what in ((src, "src"), (dst, "dst"), (ws, "ws"), (index, "index")):
+        _check_u8_cuda(t, what)
+    _call("hsrle_rle8_mmtf128_compress_indexed_dev_async", src, src.numel(), dst, dst.numel(), out_size, status, ws, ws.numel(), spacing_rows, index, index.numel(), index_size,
+          stream=stream)
+
+
+def rle8_mmtf128_index_build_dev(src, size, index, index_size, status, spacing_rows=0, stream=None):
+    """hsrle_rle8_mmtf128_index_build_dev_async: the index of the stream in `src` (of `size` uncompressed bytes), by one serial walk.  status receives
+    RLE8_MMTF_DONE or RLE8_MMTF_MALFORMED (then index_size receives 0)."""
+    for t, what in ((src, "src"), (index, "index")):
+        _check_u8_cuda(t, what)
+    _call("hsrle_rle8_mmtf128_index_build_dev_async", src, src.numel(), size, spacing_rows, index, index.numel(), index_size, status, stream=stream)
+
+
+def rle8_mmtf128_decompress_indexed_dev(src, index, info, dst, status, ws, stream=None):
+    """hsrle_rle8_mmtf128_decompress_indexed_dev_async: rle8_mmtf128_decompress_dev with the header chain followed from the entries of `index` (CUDA uint8
+    tensor; info: its Rle8MmtfIndexInfo).  status receives RLE8_MMTF_DONE, RLE8_MMTF_MALFORMED or RLE8_MMTF_INDEX (index and stream do not agree)."""
+    for t, what in ((src, "src"), (index, "index"), (dst, "dst"), (ws, "ws")):
+        _check_u8_cuda(t, what)
+    _call("hsrle_rle8_mmtf128_decompress_indexed_dev_async", src, src.numel(), index, ctypes.byref(info), dst, dst.numel(), status, ws, ws.numel(), stream=stream)
+
+
+def rle8_mmtf128_index_build_host(stream, spacing_rows=0, index_cap=None):
+    """hsrle_rle8_mmtf128_index_build_host: (status, index bytes) of a stream in host bytes."""
+    stream = bytes(stream)
+    cap = rle8_mmtf128_index_bound(int.from_bytes(stream[:4], "little"), spacing_rows) if index_cap is None else index_cap
+    out = ctypes.create_string_buffer(max(cap, 1))
+    size = ctypes.c_uint64(0)
+    rc = _lib().hsrle_rle8_mmtf128_index_build_host(stream, len(stream), spacing_rows, out, cap, ctypes.byref(size))
+    return rc, out.raw[: size.value] if rc == OK else b""
+
+
+def rle8_mmtf128_decompress_indexed_host(stream, index, out_cap):
+    """hsrle_rle8_mmtf128_decompress_indexed_host: (status, uncompressed bytes) of a stream and its index in host bytes."""
+    stream, index = bytes(stream), bytes(index)
+    out = ctypes.create_string_buffer(max(out_cap, 1))
+    size = ctypes.c_uint64(0)
+    rc = _lib().hsrle_rle8_mmtf128_decompress_indexed_host(stream, len(stream), index, len(index), out, out_cap, ctypes.byref(size))
+    return rc, out.raw[: size.value] if rc == OK else b""
 
 
 # ----------------------------------------------------------------------------------------------------------------------

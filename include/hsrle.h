@@ -705,6 +705,68 @@ int hsrle_rle8_mmtf128_decompress_dev_async(const void *dStream, uint64_t stream
 void hsrle_rle8_mmtf_tuning(uint32_t spanRows);
 
 /*
+ * The ENTRY INDEX of one rle8_mmtf128 stream: a sidecar beside the stream (the stream does not change by a byte) that names packet headers of the chain,
+ * so that the chain is followed by a wave per stretch between two entries instead of ONE wave.  Little endian, no pointers, position independent: the
+ * bytes can be stored beside the stream and loaded into any buffer at any byte address.  The same stream and spacing always give the same index bytes,
+ * whether the encoder wrote the index (compress_indexed) or the serial walk of a stream written elsewhere (index_build), whatever the tuning knobs.
+ *   64 header bytes: "HSRLEMFI", u32 version = 1, u32 headerBytes = 64, u32 uncompressedSize, u32 streamSize (the stream header's second word),
+ *     u32 spacingRows, u32 entryCount, u64 indexSize = 64 + 16 entryCount, zeros up to byte 64.
+ *   entryCount entries of 16 bytes: u32 offset (from the start of the stream, of the packet's own header byte), u32 row (the packet's first 16-byte
+ *     row), u32 ordinal (the non-null packets in front of it), u32 kind (0 COPY, 1 RLE).
+ *   THE RULE (R = uncompressedSize / 16 rows): for every j >= 1 with j spacingRows < R the first non-null packet whose first row lies in
+ *     [j spacingRows, (j + 1) spacingRows), if there is one, in order of j.  A window in which no packet begins has no entry; the chain's start (offset 8,
+ *     row 0, ordinal 0, COPY) is not stored; of an RLE packet behind an RLE packet the entry is the RLE header, not the null COPY in front of it.
+ *   spacingRows: a multiple of 64 in [64, 2^20]; 0 = 1024.  16 bytes per entry: at most 1 / spacingRows of the uncompressed size.
+ * The info struct of these calls is hsrle_mono_index_info_t (section 1), as the block containers of this section share theirs: version = 1,
+ * codec = HSRLE_RLE8_MMTF_INDEX_CODEC, compressedSize = streamSize, spacing = spacingRows, recordCount = entryCount, recordBytes = 16, streamHead = zeros,
+ * indexBytes = indexSize.  hsrle_rle8_mmtf128_index_info_t is another name of it.
+ *
+ * THE INDEX IS TRUSTED IN NOTHING.  The indexed decode checks every entry (offset inside the stream, row below R, ordinal <= row, kind <= 1, offset, row
+ * and ordinal strictly increasing) before it is used, and every stretch has to END STANDING ON the next entry's header in exactly that entry's row,
+ * ordinal and kind; the first stretch starts at the chain's true start, so an index that passes has given the very record list of the plain decode.  An
+ * index whose entries are true packet headers in order but not the rule's choice decodes correctly and is accepted: the decode proves entries, not
+ * the rule.  Everything else is HSRLE_RLE8_MMTF_INDEX: a bad entry, a missed landing, any packet of a stretch that the plain decode would refuse, an index
+ * header on the device that differs from `info`, a streamSize that is not the stream header's.  The verdict precedes every write outside the workspace;
+ * after INDEX (and MALFORMED: the stream header against the arguments, as in the plain call) nothing outside dOut[0, outSize) is touched and dOut
+ * holds nothing of use.  INDEX says that index and stream do not agree; whether the stream itself is malformed the plain call decides.
+ *
+ * hsrle_rle8_mmtf128_index_bound: an index capacity that always suffices; 0 for a bad spacing or a size above 2^30.
+ * hsrle_rle8_mmtf128_index_info_host: validates a header in host memory (magic, version, spacing, entryCount against the sizes, indexSize against
+ *   entryCount and `size`); HSRLE_ERR_FORMAT if bad.
+ * The device calls are ENQUEUE-ONLY like the calls above (a HIP graph can capture them; buffers at any byte address; dOutSize / dStatus 4-byte aligned
+ * device words, dIndexSize an 8-byte aligned device word).
+ *   compress_indexed: hsrle_rle8_mmtf128_compress_dev_async (same arguments, same workspace, the same stream byte for byte) and the index from what its
+ *     passes know: two small kernels behind it.  indexCapacity >= hsrle_rle8_mmtf128_index_bound(inSize, spacingRows), else HSRLE_ERR_CAPACITY.  On
+ *     HSRLE_RLE8_MMTF_CAPACITY *dIndexSize is 0 and no header is written.
+ *   index_build: the index of a stream written by anyone.  SERIAL BY NATURE: one wave follows the whole chain once, as the plain decode does on every
+ *     call; it pays back on every later indexed decode.  No workspace.  *dStatus: DONE, or MALFORMED as the plain decode says it; then *dIndexSize is 0
+ *     and the magic is not written.
+ *   decompress_indexed: dIndex / info: the index and its header (host, from index_info_host or built from *dIndexSize and the rule's header fields);
+ *     info->uncompressedSize == outSize, else HSRLE_ERR_ARGUMENT.  dWorkspace >= hsrle_rle8_mmtf128_workspace_size(1, outSize).  The grid is
+ *     entryCount + 1 waves: a captured call replays on any stream and index of the same sizes and entry count.
+ * The two host-pointer calls stage through the device like the functions above.  index_build_host: HSRLE_ERR_FORMAT for a malformed stream.
+ * decompress_indexed_host: HSRLE_ERR_FORMAT for a bad index header and for a decode that did not end DONE.
+ * Measured on an MI355X (profiles/r18_rle8_mmtf_index.md; 1 GiB device resident, spacing 1024, video-shaped / run-distributed / tiny packets): decompress
+ * 3 368 / 3 611 / 18 201 ms plain, 7.4 / 30.2 / 12.3 ms indexed (the walk itself 1.3 / 1.3 / 6.7 ms); 256 and 4096 rows are within 2 % of 1024 at 1 GiB.
+ * compress_indexed costs 5 ms over the plain compress at 1 GiB (15.9 -> 20.9, 92.5 -> 97.4, 13.0 -> 18.1 ms), 0.3 ms at 64 MiB; index_build costs one
+ * plain decode's walk (3.5 / 3.7 / 19.2 s).  The index is 0.40 / 0.11 / 0.45 % of the stream.
+ */
+#define HSRLE_RLE8_MMTF_INDEX 3
+#define HSRLE_RLE8_MMTF_INDEX_CODEC 0xFFFFFFFFu
+typedef hsrle_mono_index_info_t hsrle_rle8_mmtf128_index_info_t;
+uint64_t hsrle_rle8_mmtf128_index_bound(uint64_t uncompressedSize, uint32_t spacingRows);
+int hsrle_rle8_mmtf128_index_info_host(const void *pIndex, uint64_t size, hsrle_mono_index_info_t *pInfo);
+int hsrle_rle8_mmtf128_compress_indexed_dev_async(const void *dIn, uint64_t inSize, void *dOut, uint64_t outCapacity, uint32_t *dOutSize, uint32_t *dStatus, void *dWorkspace,
+                                                  uint64_t workspaceSize, uint32_t spacingRows, void *dIndex, uint64_t indexCapacity, uint64_t *dIndexSize, void *stream);
+int hsrle_rle8_mmtf128_index_build_dev_async(const void *dStream, uint64_t streamSize, uint64_t uncompressedSize, uint32_t spacingRows, void *dIndex, uint64_t indexCapacity,
+                                             uint64_t *dIndexSize, uint32_t *dStatus, void *stream);
+int hsrle_rle8_mmtf128_decompress_indexed_dev_async(const void *dStream, uint64_t streamSize, const void *dIndex, const hsrle_mono_index_info_t *info, void *dOut, uint64_t outSize,
+                                                    uint32_t *dStatus, void *dWorkspace, uint64_t workspaceSize, void *stream);
+int hsrle_rle8_mmtf128_index_build_host(const void *pStream, uint64_t streamSize, uint32_t spacingRows, void *pIndex, uint64_t indexCapacity, uint64_t *pIndexSize);
+int hsrle_rle8_mmtf128_decompress_indexed_host(const void *pStream, uint64_t streamSize, const void *pIndex, uint64_t indexSize, void *pOut, uint64_t outCapacity,
+                                               uint64_t *pUncompressedSize);
+
+/*
  * rle8_sh (src/rle_sh.c, rle.h:455-458): run-length coding with a bit stream of capped unary tokens -- one stream: u32 inSize, u32 streamSize, a body
  * of whole bytes upward from offset 8, the token bits downward from the last byte (csrc/hsrle_rle8sh.hip.h has the grammar).  Same names, arguments and
  * return values as the reference; the streams are the reference's byte for byte.
