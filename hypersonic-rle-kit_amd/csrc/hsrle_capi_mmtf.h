@@ -160,6 +160,62 @@ static bool rm_index_info_ok(const hsrle_mono_index_info_t &i)
 }
 static bool rm_index_args_ok(const void *dIndex, uint64_t *dIndexSize) { return dIndex != nullptr && dIndexSize != nullptr && word_aligned(dIndexSize, 8); }
 
+// ---- checkpoints and byte-range decode of an rle8_mmtf128 stream (kernels and layout: hsrle_rle8mmtf_range.hip.h) ----
+constexpr uint32_t kRmCheckpointDefaultRows = 65536u;   // 1 MiB of output per checkpoint: the sidecar is 0.39 % of the uncompressed size
+
+// checkpointRows as the calls take it -> rows per checkpoint, 0 = not a value
+static uint32_t rm_checkpoint_rows(uint32_t checkpointRows)
+{
+  if (checkpointRows == 0u) return kRmCheckpointDefaultRows;
+  return (checkpointRows % 64u != 0u || checkpointRows > (1u << 24)) ? 0u : checkpointRows;
+}
+static uint32_t rm_checkpoint_count(uint64_t uncompressedSize, uint32_t rows)
+{
+  const uint64_t R = uncompressedSize / 16u;
+  return R == 0u ? 0u : (uint32_t)((R - 1u) / rows);
+}
+static uint64_t rm_checkpoints_bound(uint64_t uncompressedSize, uint32_t checkpointRows)
+{
+  const uint32_t rows = rm_checkpoint_rows(checkpointRows);
+  return (rows == 0u || uncompressedSize > kRle8MmtfMaxIn) ? 0u : 64u + 4096ull * rm_checkpoint_count(uncompressedSize, rows);
+}
+static bool rm_checkpoints_info_ok(const hsrle_rle8_mmtf128_checkpoints_info_t &i)
+{
+  return i.version == 1u && i.headerBytes == 64u && i.checkpointRows != 0u && rm_checkpoint_rows(i.checkpointRows) == i.checkpointRows && i.uncompressedSize != 0u &&
+         i.uncompressedSize <= kRle8MmtfMaxIn && i.streamSize >= 10u && i.checkpointCount == rm_checkpoint_count(i.uncompressedSize, i.checkpointRows) &&
+         i.size == 64u + 4096ull * i.checkpointCount;
+}
+
+// the workspace of `rows` rows (and `tail` bytes behind them) at an index spacing
+static bool rm_range_layout(uint32_t rows, uint32_t tail, uint32_t spacing, RmRangePlan &p)
+{
+  if (!mmtf_plan(HSRLE_MMTF128, (uint64_t)rows * 16u + tail, p.mmtf))
+    return false;
+  p.maxRec = rows + 2u * spacing + 1u;   // packets of an index by the rule: at most `spacing` between e0 and row c, a row each inside, `spacing` behind r1 in the last stretch
+  p.offRanks = 256u;
+  p.offRec = p.offRanks + align_up((uint64_t)rows * 16u + 16u, 256);
+  p.offStage = p.offRec + align_up(16ull * p.maxRec, 256);
+  p.offMmtf = p.offStage + align_up((uint64_t)rows * 16u + 16u, 256);
+  p.total = 256u + p.offMmtf + p.mmtf.total;
+  return true;
+}
+// the most rows a range of `length` bytes decodes: up to checkpointRows - 1 in front of its first row
+static uint32_t rm_range_max_rows(uint64_t length, uint32_t checkpointRows) { return checkpointRows + (uint32_t)((length + 30u) / 16u); }
+
+// rows [c, r1) of a stream of `size` bytes for output bytes [offset, offset + length), length != 0, offset + length <= size
+static bool rm_range_plan(uint64_t size, uint64_t offset, uint64_t length, uint32_t spacing, uint32_t checkpointRows, RmRangePlan &p)
+{
+  const uint32_t R = (uint32_t)(size / 16u);
+  const uint64_t r0 = offset / 16u, first = R == 0u ? 0u : min64(r0, R - 1u);   // (a range of tail bytes alone: through the last row)
+  p.size = (uint32_t)size;
+  p.R = R;
+  p.c = (uint32_t)(first / checkpointRows) * checkpointRows;
+  p.r1 = (uint32_t)min64(R, (offset + length + 15u) / 16u);
+  p.skip = offset - 16ull * p.c;
+  p.stretches = (p.r1 - p.c) / spacing + 3u;   // e0's, and an entry per window that (c, r1) touches
+  return rm_range_layout(p.r1 - p.c, p.r1 == R ? p.size - 16u * R : 0u, spacing, p);
+}
+
 static const StreamCodec kRle8MmtfCodec = { hsrle_rle8_mmtf128_workspace_size, hsrle_rle8_mmtf128_compress_dev_async, hsrle_rle8_mmtf128_decompress_dev_async, kRle8MmtfMaxIn, 8u,
                                             HSRLE_RLE8_MMTF_DONE };
 
@@ -303,6 +359,147 @@ int hsrle_rle8_mmtf128_decompress_indexed_host(const void *pStream, uint64_t str
     },
     [&](const uint32_t *h, uint64_t &n) { n = info.uncompressedSize; return h[0] != HSRLE_RLE8_MMTF_DONE ? HSRLE_ERR_FORMAT : HSRLE_OK; }, pUncompressedSize,
     indexAt - streamSize + info.indexBytes);
+}
+
+// ---- checkpoints and byte-range decode ----
+uint64_t hsrle_rle8_mmtf128_checkpoints_bound(uint64_t uncompressedSize, uint32_t checkpointRows) { return rm_checkpoints_bound(uncompressedSize, checkpointRows); }
+
+int hsrle_rle8_mmtf128_checkpoints_info_host(const void *pCheckpoints, uint64_t size, void *pInfo)
+{
+  if (pCheckpoints == nullptr || pInfo == nullptr)
+    return HSRLE_ERR_ARGUMENT;
+  uint32_t w[16];
+  if (size < sizeof(w))
+    return HSRLE_ERR_FORMAT;
+  memcpy(w, pCheckpoints, sizeof(w));
+  hsrle_rle8_mmtf128_checkpoints_info_t i = {};
+  i.version = w[2]; i.headerBytes = w[3];
+  i.uncompressedSize = w[4]; i.streamSize = w[5];
+  i.checkpointRows = w[6]; i.checkpointCount = w[7];
+  i.size = (uint64_t)w[8] | (uint64_t)w[9] << 32;
+  bool zeros = true;
+  for (int k = 10; k < 16; k++) zeros = zeros && w[k] == 0u;
+  if (memcmp(w, "HSRLEMFC", 8) != 0 || !zeros || !rm_checkpoints_info_ok(i) || i.size > size)
+    return HSRLE_ERR_FORMAT;
+  *(hsrle_rle8_mmtf128_checkpoints_info_t *)pInfo = i;
+  return HSRLE_OK;
+}
+
+int hsrle_rle8_mmtf128_checkpoints_build_dev_async(const void *dStream, uint64_t streamSize, const void *dIndex, const hsrle_mono_index_info_t *indexInfo, uint32_t checkpointRows,
+                                                   void *dCheckpoints, uint64_t capacity, uint64_t *dSize, uint32_t *dStatus, void *dWorkspace, uint64_t workspaceSize,
+                                                   void *stream)
+{
+  const uint32_t rows = rm_checkpoint_rows(checkpointRows);
+  Rle8MmtfPlan p;
+  if (dStream == nullptr || dIndex == nullptr || indexInfo == nullptr || dCheckpoints == nullptr || dSize == nullptr || dStatus == nullptr || dWorkspace == nullptr ||
+      streamSize == 0u || rows == 0u || !rm_index_info_ok(*indexInfo) || !rle8mmtf_dec_plan(indexInfo->uncompressedSize, p))
+    return HSRLE_ERR_ARGUMENT;
+  if (!word_aligned(dSize, 8) || !word_aligned(dStatus, 4) || ranges_overlap(dCheckpoints, capacity, dStream, streamSize) ||
+      ranges_overlap(dCheckpoints, capacity, dIndex, indexInfo->indexBytes))
+    return HSRLE_ERR_ARGUMENT;
+  if (capacity < rm_checkpoints_bound(p.size, rows) || workspaceSize < p.total)
+    return HSRLE_ERR_CAPACITY;
+  return rle8mmtf_checkpoints_build_enqueue(p, (const uint8_t *)dStream, clamp32(streamSize), (const uint8_t *)dIndex, indexInfo->compressedSize, indexInfo->spacing,
+                                            indexInfo->recordCount, rows, rm_checkpoint_count(p.size, rows), (uint8_t *)dCheckpoints, dSize, dStatus, workspace_start(dWorkspace),
+                                            (hipStream_t)stream) == hipSuccess
+           ? HSRLE_OK
+           : HSRLE_ERR_DEVICE;
+}
+
+uint64_t hsrle_rle8_mmtf128_range_workspace_size(uint64_t length, uint32_t spacingRows, uint32_t checkpointRows)
+{
+  const uint32_t spacing = rm_index_spacing(spacingRows), rows = rm_checkpoint_rows(checkpointRows);
+  RmRangePlan p;
+  if (length == 0u || length > kRle8MmtfMaxIn || spacing == 0u || rows == 0u || !rm_range_layout(rm_range_max_rows(length, rows), 15u, spacing, p))
+    return 0u;
+  return p.total;
+}
+
+int hsrle_rle8_mmtf128_decompress_range_dev_async(const void *dStream, uint64_t streamSize, const void *dIndex, const hsrle_mono_index_info_t *indexInfo, const void *dCheckpoints,
+                                                  const void *checkpointsInfo, uint64_t offset, uint64_t length, void *dOut, uint64_t outCapacity, uint32_t *dStatus,
+                                                  void *dWorkspace, uint64_t workspaceSize, void *stream)
+{
+  const hsrle_rle8_mmtf128_checkpoints_info_t *ck = (const hsrle_rle8_mmtf128_checkpoints_info_t *)checkpointsInfo;
+  if (dStream == nullptr || dIndex == nullptr || indexInfo == nullptr || dCheckpoints == nullptr || ck == nullptr || dOut == nullptr || dStatus == nullptr ||
+      dWorkspace == nullptr || streamSize == 0u || !rm_index_info_ok(*indexInfo) || !rm_checkpoints_info_ok(*ck) || !word_aligned(dStatus, 4))
+    return HSRLE_ERR_ARGUMENT;
+  const uint64_t size = indexInfo->uncompressedSize;
+  if (ck->uncompressedSize != size || ck->streamSize != indexInfo->compressedSize || offset > size || length > size - offset || outCapacity < length ||
+      ranges_overlap(dOut, length, dStream, streamSize) || ranges_overlap(dOut, length, dIndex, indexInfo->indexBytes) || ranges_overlap(dOut, length, dCheckpoints, ck->size))
+    return HSRLE_ERR_ARGUMENT;
+  if (length == 0u)
+    return HSRLE_OK;
+  RmRangePlan p;
+  if (!rm_range_plan(size, offset, length, indexInfo->spacing, ck->checkpointRows, p))
+    return HSRLE_ERR_ARGUMENT;
+  if (workspaceSize < p.total)
+    return HSRLE_ERR_CAPACITY;
+  return rle8mmtf_decompress_range_enqueue(p, (const uint8_t *)dStream, clamp32(streamSize), (const uint8_t *)dIndex, indexInfo->compressedSize, indexInfo->spacing,
+                                           indexInfo->recordCount, (const uint8_t *)dCheckpoints, ck->checkpointRows, ck->checkpointCount, (uint8_t *)dOut, length, dStatus,
+                                           workspace_start(dWorkspace), (hipStream_t)stream) == hipSuccess
+           ? HSRLE_OK
+           : HSRLE_ERR_DEVICE;
+}
+
+// The two host-pointer calls: the staged trip, the sidecars behind the stream in the input staging.  Status word and size word: Staging::status[0] and [2 .. 3].
+int hsrle_rle8_mmtf128_checkpoints_build_host(const void *pStream, uint64_t streamSize, const void *pIndex, uint64_t indexSize, uint32_t checkpointRows, void *pCheckpoints,
+                                              uint64_t capacity, uint64_t *pSize)
+{
+  if (pStream == nullptr || pIndex == nullptr || pCheckpoints == nullptr || pSize == nullptr || streamSize < 8u || streamSize > 0xFFFFFFFFull ||
+      rm_checkpoint_rows(checkpointRows) == 0u)
+    return HSRLE_ERR_ARGUMENT;
+  hsrle_mono_index_info_t info;
+  const int rc = hsrle_rle8_mmtf128_index_info_host(pIndex, indexSize, &info);
+  if (rc != HSRLE_OK)
+    return rc;
+  const uint64_t bound = rm_checkpoints_bound(info.uncompressedSize, checkpointRows);
+  if (capacity < bound)
+    return HSRLE_ERR_CAPACITY;
+  const uint64_t need = hsrle_rle8_mmtf128_workspace_size(1, info.uncompressedSize), indexAt = align_up(streamSize, 256);
+  if (need == 0u || !device_ok())
+    return HSRLE_ERR_DEVICE;
+  return staged_call(
+    pStream, streamSize, bound, need, pCheckpoints, 4u,
+    [&](Staging &s) {
+      if (!s.up(pIndex, info.indexBytes, indexAt))
+        return (int)HSRLE_ERR_DEVICE;
+      return hsrle_rle8_mmtf128_checkpoints_build_dev_async(s.in, streamSize, s.in + indexAt, &info, checkpointRows, s.out, bound, (uint64_t *)(s.status + 2), s.status, s.ws,
+                                                            s.wsSize, nullptr);
+    },
+    [&](const uint32_t *h, uint64_t &n) { n = (uint64_t)h[2] | (uint64_t)h[3] << 32; return h[0] != HSRLE_RLE8_MMTF_DONE || n != bound ? HSRLE_ERR_FORMAT : HSRLE_OK; }, pSize,
+    indexAt - streamSize + info.indexBytes);
+}
+
+int hsrle_rle8_mmtf128_decompress_range_host(const void *pStream, uint64_t streamSize, const void *pIndex, uint64_t indexSize, const void *pCheckpoints, uint64_t checkpointsSize,
+                                             uint64_t offset, uint64_t length, void *pOut, uint64_t outCapacity)
+{
+  if (pStream == nullptr || pIndex == nullptr || pCheckpoints == nullptr || pOut == nullptr || streamSize < 8u || streamSize > 0xFFFFFFFFull)
+    return HSRLE_ERR_ARGUMENT;
+  hsrle_mono_index_info_t info;
+  hsrle_rle8_mmtf128_checkpoints_info_t ck;
+  int rc = hsrle_rle8_mmtf128_index_info_host(pIndex, indexSize, &info);
+  if (rc == HSRLE_OK) rc = hsrle_rle8_mmtf128_checkpoints_info_host(pCheckpoints, checkpointsSize, &ck);
+  if (rc != HSRLE_OK)
+    return rc;
+  if (ck.uncompressedSize != info.uncompressedSize || ck.streamSize != info.compressedSize || offset > info.uncompressedSize || length > info.uncompressedSize - offset ||
+      outCapacity < length)
+    return HSRLE_ERR_ARGUMENT;
+  if (length == 0u)
+    return HSRLE_OK;
+  const uint64_t need = hsrle_rle8_mmtf128_range_workspace_size(length, info.spacing, ck.checkpointRows), indexAt = align_up(streamSize, 256),
+                 ckAt = align_up(indexAt + info.indexBytes, 256);
+  if (need == 0u || !device_ok())
+    return HSRLE_ERR_DEVICE;
+  uint64_t copied = 0;
+  return staged_call(
+    pStream, streamSize, length, need, pOut, 1u,
+    [&](Staging &s) {
+      if (!s.up(pIndex, info.indexBytes, indexAt) || !s.up(pCheckpoints, ck.size, ckAt))
+        return (int)HSRLE_ERR_DEVICE;
+      return hsrle_rle8_mmtf128_decompress_range_dev_async(s.in, streamSize, s.in + indexAt, &info, s.in + ckAt, &ck, offset, length, s.out, length, s.status, s.ws, s.wsSize,
+                                                           nullptr);
+    },
+    [&](const uint32_t *h, uint64_t &n) { n = length; return h[0] != HSRLE_RLE8_MMTF_DONE ? HSRLE_ERR_FORMAT : HSRLE_OK; }, &copied, ckAt - streamSize + ck.size);
 }
 
 uint32_t rle8_mmtf128_compress_bounds(const uint32_t inSize) { return rle8mmtf_bounds(inSize); }

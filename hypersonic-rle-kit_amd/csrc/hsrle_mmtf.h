@@ -40,6 +40,34 @@ hipError_t rle8mmtf_index_build_enqueue(const uint8_t *dStream, uint32_t streamC
 hipError_t rle8mmtf_decompress_indexed_enqueue(const Rle8MmtfPlan &p, const uint8_t *dStream, uint32_t streamCap, const uint8_t *dIndex, uint32_t streamSize, uint32_t spacing,
                                                uint32_t entries, uint8_t *dOut, uint32_t *dStatus, uint8_t *ws, hipStream_t st);
 
+// The first two launches of decompress_indexed and its third: the whole stream's rank buffer and ctrl[0] (the verdict, also in *dStatus), ctrl[3] (the stream's size).
+hipError_t rle8mmtf_expand_indexed_enqueue(const Rle8MmtfPlan &p, const uint8_t *dStream, uint32_t streamCap, const uint8_t *dIndex, uint32_t streamSize, uint32_t spacing,
+                                           uint32_t entries, uint32_t *dStatus, uint8_t *ws, hipStream_t st);
+// mmtf128 decode without its last pass (inst_mmtf.hip): pass A, and with `scan` pass B, which leaves the list in front of segment s in slot s of the state table.
+// Nothing for a plan of one segment.
+hipError_t mmtf128_decode_segments_enqueue(const MmtfPlan &p, const uint8_t *dIn, uint8_t *ws, bool scan, hipStream_t st);
+
+// Checkpoints and byte-range decode of one rle8_mmtf128 stream (kernels: hsrle_rle8mmtf_range.hip.h; launched by inst_rle8mmtfr.hip).  checkpoints_build: the decode
+// plan and workspace of decompress_enqueue.  decompress_range: rows [c, r1) are decoded from the checkpoint of row c (c = 0: from the identity) and output bytes
+// [skip, skip + length) of them copied out.  Workspace, from its 256-byte aligned start: control words, the rank buffer of the rows, the packet records, the staging
+// area, the workspace of the mmtf128 plan of the rows.
+struct RmRangePlan
+{
+  MmtfPlan mmtf;                    // of the r1 - c rows, and the tail bytes if r1 = R
+  uint32_t size = 0, R = 0;         // the whole stream: uncompressed bytes, rows
+  uint32_t c = 0, r1 = 0;
+  uint32_t maxRec = 0;              // records the table holds
+  uint32_t stretches = 0;           // a bound on the stretches that reach into [c, r1): the walk's grid
+  uint64_t skip = 0;
+  uint64_t offRanks = 0, offRec = 0, offStage = 0, offMmtf = 0, total = 0;
+};
+hipError_t rle8mmtf_checkpoints_build_enqueue(const Rle8MmtfPlan &p, const uint8_t *dStream, uint32_t streamCap, const uint8_t *dIndex, uint32_t streamSize, uint32_t spacing,
+                                              uint32_t entries, uint32_t checkpointRows, uint32_t count, uint8_t *dCheckpoints, uint64_t *dSize, uint32_t *dStatus, uint8_t *ws,
+                                              hipStream_t st);
+hipError_t rle8mmtf_decompress_range_enqueue(const RmRangePlan &p, const uint8_t *dStream, uint32_t streamCap, const uint8_t *dIndex, uint32_t streamSize, uint32_t spacing,
+                                             uint32_t entries, const uint8_t *dCheckpoints, uint32_t checkpointRows, uint32_t count, uint8_t *dOut, uint64_t length,
+                                             uint32_t *dStatus, uint8_t *ws, hipStream_t st);
+
 // The blocked form (hsrle_capi_mmtfb.h plans, inst_rle8mmtfb.hip launches, kernels: hsrle_rle8mmtfb.hip.h).  Workspace, from its 256-byte aligned start:
 // 256 bytes of words for the whole call, then `inFlight` SLOTS: control words, the block's rank buffer, then -- encode: the span summaries and the span
 // results of a block; decode: its packet records.

@@ -38,6 +38,19 @@ static hipError_t bitmmtf_enqueue(const MmtfPlan &p, bool decode, const uint8_t 
   return hipGetLastError();
 }
 
+hipError_t mmtf128_decode_segments_enqueue(const MmtfPlan &p, const uint8_t *dIn, uint8_t *ws, bool scan, hipStream_t st)
+{
+  if (p.S <= 1u) return hipSuccess;
+  MmtfArgs a;
+  a.in = dIn; a.out = nullptr;
+  a.table = (uint32_t *)(ws + p.offTable);
+  a.counts = (uint32_t *)(ws + p.offCounts);
+  a.size = p.size; a.rows = p.rows; a.R = p.R; a.S = p.S;
+  hipLaunchKernelGGL((k_mmtf_rows<16, true, false>), dim3((uint32_t)(((uint64_t)(a.S - 1u) * 16u + 63u) / 64u)), dim3(64), 0, st, a);
+  if (scan) hipLaunchKernelGGL((k_mmtf_scan_dec<16>), dim3(16), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
 hipError_t mmtf_enqueue(const MmtfPlan &p, bool decode, const uint8_t *dIn, uint8_t *dOut, uint8_t *ws, hipStream_t st)
 {
   if (p.E != 0u)

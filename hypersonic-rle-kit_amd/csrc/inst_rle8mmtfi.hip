@@ -42,8 +42,8 @@ hipError_t rle8mmtf_index_build_enqueue(const uint8_t *dStream, uint32_t streamC
   return hipGetLastError();
 }
 
-hipError_t rle8mmtf_decompress_indexed_enqueue(const Rle8MmtfPlan &p, const uint8_t *dStream, uint32_t streamCap, const uint8_t *dIndex, uint32_t streamSize, uint32_t spacing,
-                                               uint32_t entries, uint8_t *dOut, uint32_t *dStatus, uint8_t *ws, hipStream_t st)
+hipError_t rle8mmtf_expand_indexed_enqueue(const Rle8MmtfPlan &p, const uint8_t *dStream, uint32_t streamCap, const uint8_t *dIndex, uint32_t streamSize, uint32_t spacing,
+                                           uint32_t entries, uint32_t *dStatus, uint8_t *ws, hipStream_t st)
 {
   RmIdxDecArgs a;
   a.d.stream = dStream;
@@ -59,7 +59,13 @@ hipError_t rle8mmtf_decompress_indexed_enqueue(const Rle8MmtfPlan &p, const uint
   hipLaunchKernelGGL((k_rm_walk_indexed<0>), dim3(entries + 1u), dim3(64), 0, st, a);
   const uint32_t wg = (p.rows + 255u) / 256u;
   hipLaunchKernelGGL((k_rm_expand_indexed<0>), dim3(wg ? wg : 1u), dim3(256), 0, st, a.d);
-  const hipError_t e = hipGetLastError();
+  return hipGetLastError();
+}
+
+hipError_t rle8mmtf_decompress_indexed_enqueue(const Rle8MmtfPlan &p, const uint8_t *dStream, uint32_t streamCap, const uint8_t *dIndex, uint32_t streamSize, uint32_t spacing,
+                                               uint32_t entries, uint8_t *dOut, uint32_t *dStatus, uint8_t *ws, hipStream_t st)
+{
+  const hipError_t e = rle8mmtf_expand_indexed_enqueue(p, dStream, streamCap, dIndex, streamSize, spacing, entries, dStatus, ws, st);
   if (e != hipSuccess) return e;
   return mmtf_enqueue(p.mmtf, true, ws + p.offRanks, dOut, ws + p.offMmtf, st);
 }

@@ -84,7 +84,8 @@ class Rle8mInfo(ctypes.Structure):
 # ----------------------------------------------------------------------------------------------------------------------
 # the signatures of include/hsrle.h as data: symbol -> (restype, argtypes).  tests/test_binding_signatures.py holds them against the header's prototypes:
 # a pointer to void or to an integer is c_void_p (POINTER of the integer where a caller passes byref of one), const char * is c_char_p, a pointer to one of
-# the four info structs is POINTER of its class above, every other struct pointer is c_void_p, scalars are themselves.
+# the four info structs is POINTER of its class above, every other struct pointer is c_void_p, scalars are themselves.  (The checkpoint sidecar's info struct,
+# Rle8MmtfCheckpointsInfo below, is declared void * in the header for that reason.)
 
 
 def _signatures():
@@ -189,6 +190,13 @@ def _signatures():
         "hsrle_rle8_mmtf128_decompress_indexed_dev_async": (ci, [vp, u64, vp, idx, vp, u64, vp, vp, u64, vp]),
         "hsrle_rle8_mmtf128_index_build_host": (ci, [vp, u64, u32, vp, u64, P(u64)]),
         "hsrle_rle8_mmtf128_decompress_indexed_host": (ci, [vp, u64, vp, u64, vp, u64, P(u64)]),
+        "hsrle_rle8_mmtf128_checkpoints_bound": (u64, [u64, u32]),
+        "hsrle_rle8_mmtf128_checkpoints_info_host": (ci, [vp, u64, vp]),                    # (the info: Rle8MmtfCheckpointsInfo, through void * in the header)
+        "hsrle_rle8_mmtf128_checkpoints_build_dev_async": (ci, [vp, u64, vp, idx, u32, vp, u64, vp, vp, vp, u64, vp]),
+        "hsrle_rle8_mmtf128_range_workspace_size": (u64, [u64, u32, u32]),
+        "hsrle_rle8_mmtf128_decompress_range_dev_async": (ci, [vp, u64, vp, idx, vp, vp, u64, u64, vp, u64, vp, vp, u64, vp]),
+        "hsrle_rle8_mmtf128_checkpoints_build_host": (ci, [vp, u64, vp, u64, u32, vp, u64, P(u64)]),
+        "hsrle_rle8_mmtf128_decompress_range_host": (ci, [vp, u64, vp, u64, vp, u64, u64, u64, vp, u64]),
         "hsrle_rle8_sh_workspace_size": (u64, [ci, u64]),
         "hsrle_rle8_sh_capacity": (u64, [u64]),
         "hsrle_rle8_sh_compress_dev_async": stream_enc,
@@ -979,6 +987,84 @@ def rle8_mmtf128_decompress_indexed_host(stream, index, out_cap):
     size = ctypes.c_uint64(0)
     rc = _lib().hsrle_rle8_mmtf128_decompress_indexed_host(stream, len(stream), index, len(index), out, out_cap, ctypes.byref(size))
     return rc, out.raw[: size.value] if rc == OK else b""
+
+
+# checkpoints of one rle8_mmtf128 stream (the sixteen lists in front of every checkpointRows-th row) and the byte-range decode from index and checkpoints
+
+RLE8_MMTF_CHECKPOINT = 4
+
+
+class Rle8MmtfCheckpointsInfo(ctypes.Structure):
+    """hsrle_rle8_mmtf128_checkpoints_info_t: the header of the checkpoint sidecar of one rle8_mmtf128 stream."""
+
+    _fields_ = [
+        ("version", ctypes.c_uint32),
+        ("headerBytes", ctypes.c_uint32),
+        ("uncompressedSize", ctypes.c_uint32),
+        ("streamSize", ctypes.c_uint32),
+        ("checkpointRows", ctypes.c_uint32),
+        ("checkpointCount", ctypes.c_uint32),
+        ("size", ctypes.c_uint64),
+    ]
+
+
+def rle8_mmtf128_checkpoints_bound(size, checkpoint_rows=0):
+    """hsrle_rle8_mmtf128_checkpoints_bound: the exact size of the sidecar (0: bad checkpoint_rows, size above 2^30).  checkpoint_rows 0 = the default."""
+    return int(_lib().hsrle_rle8_mmtf128_checkpoints_bound(size, checkpoint_rows))
+
+
+def rle8_mmtf128_checkpoints_info(checkpoints):
+    """hsrle_rle8_mmtf128_checkpoints_info_host on sidecar bytes: the validated header as Rle8MmtfCheckpointsInfo; raises HsrleError(ERR_FORMAT) for a bad one."""
+    checkpoints = bytes(checkpoints)
+    info = Rle8MmtfCheckpointsInfo()
+    rc = _lib().hsrle_rle8_mmtf128_checkpoints_info_host(checkpoints, len(checkpoints), ctypes.byref(info))
+    if rc != OK:
+        raise HsrleError(rc, "hsrle_rle8_mmtf128_checkpoints_info_host")
+    return info
+
+
+def rle8_mmtf128_range_workspace_size(length, spacing_rows=0, checkpoint_rows=0):
+    """hsrle_rle8_mmtf128_range_workspace_size: bytes of device workspace of a range decode of `length` bytes (0: bad arguments)."""
+    return int(_lib().hsrle_rle8_mmtf128_range_workspace_size(length, spacing_rows, checkpoint_rows))
+
+
+def rle8_mmtf128_checkpoints_build_dev(src, index, info, checkpoints, size, status, ws, checkpoint_rows=0, stream=None):
+    """hsrle_rle8_mmtf128_checkpoints_build_dev_async: the checkpoints of the stream in `src` with its index (info: Rle8MmtfIndexInfo) into the CUDA uint8
+    tensor `checkpoints` (>= rle8_mmtf128_checkpoints_bound bytes).  size: CUDA int64 tensor of one element, receives the sidecar's size; status receives
+    RLE8_MMTF_DONE, or RLE8_MMTF_MALFORMED / RLE8_MMTF_INDEX (then size receives 0).  ws: rle8_mmtf128_workspace_size(True, n) bytes."""
+    for t, what in ((src, "src"), (index, "index"), (checkpoints, "checkpoints"), (ws, "ws")):
+        _check_u8_cuda(t, what)
+    _call("hsrle_rle8_mmtf128_checkpoints_build_dev_async", src, src.numel(), index, ctypes.byref(info), checkpoint_rows, checkpoints, checkpoints.numel(), size, status, ws,
+          ws.numel(), stream=stream)
+
+
+def rle8_mmtf128_decompress_range_dev(src, index, info, checkpoints, checkpoints_info, offset, length, dst, status, ws, stream=None):
+    """hsrle_rle8_mmtf128_decompress_range_dev_async: output bytes [offset, offset + length) of the stream in `src` into dst[0, length), from its index and
+    checkpoints (CUDA uint8 tensors; info, checkpoints_info: their headers).  status receives RLE8_MMTF_DONE, _MALFORMED, _INDEX or _CHECKPOINT; dst is
+    written behind DONE only.  ws: rle8_mmtf128_range_workspace_size(length, info.spacing, checkpoints_info.checkpointRows) bytes."""
+    for t, what in ((src, "src"), (index, "index"), (checkpoints, "checkpoints"), (dst, "dst"), (ws, "ws")):
+        _check_u8_cuda(t, what)
+    _call("hsrle_rle8_mmtf128_decompress_range_dev_async", src, src.numel(), index, ctypes.byref(info), checkpoints, ctypes.byref(checkpoints_info), offset, length, dst,
+          dst.numel(), status, ws, ws.numel(), stream=stream)
+
+
+def rle8_mmtf128_checkpoints_build_host(stream, index, checkpoint_rows=0, cap=None):
+    """hsrle_rle8_mmtf128_checkpoints_build_host: (status, sidecar bytes) of a stream and its index in host bytes."""
+    stream, index = bytes(stream), bytes(index)
+    cap = rle8_mmtf128_checkpoints_bound(int.from_bytes(stream[:4], "little"), checkpoint_rows) if cap is None else cap
+    out = ctypes.create_string_buffer(max(cap, 1))
+    size = ctypes.c_uint64(0)
+    rc = _lib().hsrle_rle8_mmtf128_checkpoints_build_host(stream, len(stream), index, len(index), checkpoint_rows, out, cap, ctypes.byref(size))
+    return rc, out.raw[: size.value] if rc == OK else b""
+
+
+def rle8_mmtf128_decompress_range_host(stream, index, checkpoints, offset, length, out_cap=None):
+    """hsrle_rle8_mmtf128_decompress_range_host: (status, output bytes [offset, offset + length)) of a stream and its two sidecars in host bytes."""
+    stream, index, checkpoints = bytes(stream), bytes(index), bytes(checkpoints)
+    cap = length if out_cap is None else out_cap
+    out = ctypes.create_string_buffer(max(cap, 1))
+    rc = _lib().hsrle_rle8_mmtf128_decompress_range_host(stream, len(stream), index, len(index), checkpoints, len(checkpoints), offset, length, out, cap)
+    return rc, out.raw[:length] if rc == OK else b""
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -767,6 +767,71 @@ int hsrle_rle8_mmtf128_decompress_indexed_host(const void *pStream, uint64_t str
                                                uint64_t *pUncompressedSize);
 
 /*
+ * BYTE-RANGE DECODE of one rle8_mmtf128 stream, and the CHECKPOINTS it needs: a second sidecar beside the stream and its entry index (neither changes by a
+ * byte).  The index lets the header chain be entered in the middle; the sixteen move-to-front lists at a range's start depend on every byte in front of it,
+ * and the checkpoints hold them.  Little endian, no pointers, position independent, at any byte address.
+ *   64 header bytes: "HSRLEMFC", u32 version = 1, u32 headerBytes = 64, u32 uncompressedSize, u32 streamSize, u32 checkpointRows, u32 checkpointCount,
+ *     u64 size = 64 + 4096 checkpointCount, zeros up to byte 64.
+ *   checkpointCount checkpoints of 4096 bytes: checkpoint k = 1 .. count holds the sixteen lists of mmtf128 as they stand in front of row k checkpointRows,
+ *     column c's at bytes [256 c, 256 c + 256), byte i the symbol of rank i.  With R = uncompressedSize / 16 rows, checkpointCount = (R - 1) / checkpointRows
+ *     (0 for R = 0): row 0 is the identity and not stored, and there is none for the tail -- a range that touches the uncompressedSize % 16 tail bytes is
+ *     decoded through row R.
+ *   checkpointRows: a multiple of 64 in [64, 2^24]; 0 = 65 536 (1 MiB of output per checkpoint, 0.39 % of the uncompressed size).
+ *   The lists are a function of the uncompressed bytes alone: the same data and checkpointRows give the same sidecar bytes, whatever the tuning knobs.
+ * hsrle_rle8_mmtf128_checkpoints_info_t holds the header's fields.  The calls below take it through a void pointer (`checkpointsInfo`, `pInfo`): it always
+ * points to this struct.
+ *
+ * NEITHER SIDECAR IS TRUSTED FOR MEMORY SAFETY.  Every entry and every packet is bounds-checked as in the indexed decode, the records a stretch may write are
+ * bounded before it is walked, and a rank only ever indexes a 256-entry list: any bytes in either sidecar leave everything outside dOut[0, length) and the
+ * workspace untouched.  But a range decode CANNOT PROVE CONTENT the way the whole indexed decode does: its first stretch starts from an entry that nothing
+ * in front of it vouches for, and a checkpoint that is a permutation of 0 .. 255 but the wrong one gives wrong bytes with HSRLE_RLE8_MMTF_DONE.  The landing
+ * rule still proves that consecutive entries inside the range agree with the stream.  The arbiter of both sidecars is decompress_indexed of the whole stream,
+ * and checkpoints_build run again.  The record table is sized for an index by the rule (at most spacingRows packets between an entry and the range): a sparser
+ * index of true headers, which decompress_indexed accepts, can end in HSRLE_RLE8_MMTF_INDEX here.
+ *
+ * hsrle_rle8_mmtf128_checkpoints_bound: the exact sidecar size; 0 for a bad checkpointRows or a size above 2^30.
+ * hsrle_rle8_mmtf128_checkpoints_info_host: validates a header in host memory (magic, version, checkpointRows, the count against the sizes, `size`);
+ *   HSRLE_ERR_FORMAT if bad.
+ * The device calls are ENQUEUE-ONLY (a HIP graph can capture them; buffers at any byte address; dStatus a 4-byte aligned device word, dSize 8-byte aligned).
+ *   checkpoints_build: from any stream and its index (indexInfo: its header, as for decompress_indexed).  One indexed decode without its last pass, and a
+ *     lane per (checkpoint, column) behind it; a stream without an index pays index_build's serial walk first, once.  dWorkspace >=
+ *     hsrle_rle8_mmtf128_workspace_size(1, uncompressedSize); capacity >= checkpoints_bound, else HSRLE_ERR_CAPACITY.  *dStatus: DONE, or MALFORMED / INDEX
+ *     exactly as decompress_indexed says them; then *dSize is 0 and the magic is not written.
+ *   decompress_range: output bytes [offset, offset + length) to dOut[0, length); nothing outside it and the workspace is written.  Only the stretches from the
+ *     last entry at or in front of the checkpoint row c <= offset / 16 to the range's end are walked, only rows [c, end) expanded and transformed, from
+ *     checkpoint c's lists (c = 0: the identity, no checkpoint is read).  length == 0: HSRLE_OK, nothing enqueued.  offset + length > uncompressedSize,
+ *     outCapacity < length, two infos that disagree in uncompressedSize or streamSize: HSRLE_ERR_ARGUMENT, nothing enqueued.  dWorkspace >=
+ *     hsrle_rle8_mmtf128_range_workspace_size(length, spacingRows, checkpointRows): a function of the range and the two spacings, never of the stream's size
+ *     (0 for bad arguments).  *dStatus: DONE; MALFORMED (the stream header against the arguments); INDEX (the index header on the device differs from
+ *     indexInfo, a bad entry, a missed landing, a packet the plain decode would refuse, a stretch with more packets than the record table holds); CHECKPOINT
+ *     (the header on the device differs from checkpointsInfo, or a list of the checkpoint the range starts from is not a permutation of 0 .. 255).  Every
+ *     verdict precedes every write to dOut: behind anything but DONE dOut is untouched.  A captured call replays on any stream, index and checkpoints of the
+ *     same sizes and counts, for the same range.
+ * The two host-pointer calls stage through the device like the functions above; HSRLE_ERR_FORMAT for a bad sidecar header and for a status that is not DONE.
+ */
+#define HSRLE_RLE8_MMTF_CHECKPOINT 4
+typedef struct hsrle_rle8_mmtf128_checkpoints_info
+{
+  uint32_t version, headerBytes;               /* 1, 64 */
+  uint32_t uncompressedSize, streamSize;       /* as in the stream's header */
+  uint32_t checkpointRows, checkpointCount;    /* checkpointCount = (uncompressedSize / 16 - 1) / checkpointRows */
+  uint64_t size;                               /* 64 + 4096 checkpointCount */
+} hsrle_rle8_mmtf128_checkpoints_info_t;
+uint64_t hsrle_rle8_mmtf128_checkpoints_bound(uint64_t uncompressedSize, uint32_t checkpointRows);
+int hsrle_rle8_mmtf128_checkpoints_info_host(const void *pCheckpoints, uint64_t size, void *pInfo);
+int hsrle_rle8_mmtf128_checkpoints_build_dev_async(const void *dStream, uint64_t streamSize, const void *dIndex, const hsrle_mono_index_info_t *indexInfo, uint32_t checkpointRows,
+                                                   void *dCheckpoints, uint64_t capacity, uint64_t *dSize, uint32_t *dStatus, void *dWorkspace, uint64_t workspaceSize,
+                                                   void *stream);
+uint64_t hsrle_rle8_mmtf128_range_workspace_size(uint64_t length, uint32_t spacingRows, uint32_t checkpointRows);
+int hsrle_rle8_mmtf128_decompress_range_dev_async(const void *dStream, uint64_t streamSize, const void *dIndex, const hsrle_mono_index_info_t *indexInfo, const void *dCheckpoints,
+                                                  const void *checkpointsInfo, uint64_t offset, uint64_t length, void *dOut, uint64_t outCapacity, uint32_t *dStatus,
+                                                  void *dWorkspace, uint64_t workspaceSize, void *stream);
+int hsrle_rle8_mmtf128_checkpoints_build_host(const void *pStream, uint64_t streamSize, const void *pIndex, uint64_t indexSize, uint32_t checkpointRows, void *pCheckpoints,
+                                              uint64_t capacity, uint64_t *pSize);
+int hsrle_rle8_mmtf128_decompress_range_host(const void *pStream, uint64_t streamSize, const void *pIndex, uint64_t indexSize, const void *pCheckpoints, uint64_t checkpointsSize,
+                                             uint64_t offset, uint64_t length, void *pOut, uint64_t outCapacity);
+
+/*
  * rle8_sh (src/rle_sh.c, rle.h:455-458): run-length coding with a bit stream of capped unary tokens -- one stream: u32 inSize, u32 streamSize, a body
  * of whole bytes upward from offset 8, the token bits downward from the last byte (csrc/hsrle_rle8sh.hip.h has the grammar).  Same names, arguments and
  * return values as the reference; the streams are the reference's byte for byte.
